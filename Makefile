@@ -10,7 +10,7 @@ VERSION     := $(shell $(PYTHON) -c "from otedama_amd.version import VERSION; pr
 
 export PYTHONPATH := $(CURDIR)$(if $(PYTHONPATH),:$(PYTHONPATH))
 
-.PHONY: help build rebuild test test-unit test-gpu test-multiproc bench bench-cpu profile fuzz lint docs \
+.PHONY: help build rebuild test test-unit test-gpu test-multiproc bench bench-full bench-cpu profile fuzz lint docs \
         docker-build docker-run release-check clean smoke doctor sanitize
 
 help: ## Display this help message
@@ -36,6 +36,9 @@ test-gpu: build ## GPU tests + bench on a real MI355X through gpurun
 
 bench: build ## Headline benchmark (1 GPU; use torchrun for N>1, see README)
 	$(PYTHON) bench.py
+
+bench-full: build ## Headline benchmark plus every other section (scrypt, X11, CPU, latency, node, pool)
+	$(PYTHON) bench.py --full
 
 bench-cpu: build ## Reference-style single-thread CPU SHA-256d benchmark
 	$(PYTHON) -m otedama_amd bench --device cpu --threads 1

@@ -17,7 +17,10 @@ under deadlines watched by a thread that never waits on the main thread:
              the ranks that checked in, each rank's phase, the tail of its
              stderr and of its RCCL log (NCCL_DEBUG=WARN), and exits non-zero;
   sha256d    the headline (below);
-  single, scrypt, x11, miner   all ranks; cpu, latency, node, pool   rank 0.
+and, with ``--full`` only,
+  single, scrypt, x11, miner, comm   all ranks; cpu, latency, node, pool   rank 0.
+A plain run sets up, warms up, times the --steps steps, re-verifies their hits and prints the line; the keys of the
+other sections are null in it.
 A section that overruns its budget (or the run's --deadline) is recorded as
 {"error": "timeout after X s"} and the JSON is printed with everything measured
 so far; a SIGTERM (torchrun tearing the job down, the driver's timeout) makes
@@ -40,7 +43,10 @@ target = difficulty 1. Every hit of the timed region is de-duplicated by
 (header variant, nonce), re-verified on the CPU, and compared with the Poisson
 expectation (z-score). Weak scaling: per-GPU work is fixed as N grows.
 
-Then BASELINE config 2 verbatim (one fixed midstate, full 2^32 nonces, the
+``--dump-outputs DIR`` writes what the last timed step returned (its hit slot, sorted) and every timed step's hits as
+DIR/<name>.npy (Bench.dump_outputs); the headers depend on --seed alone, so equal arguments give equal files.
+
+Then, with ``--full``, BASELINE config 2 verbatim (one fixed midstate, full 2^32 nonces, the
 single-header kernel), scrypt(1024,1,1) (HBM-resident scratchpads; hits re-
 verified with hashlib.scrypt), X11 (nonce ranges partitioned across ranks; hits
 re-verified with the C++ chain), scrypt and X11 through the production miner,
@@ -52,7 +58,7 @@ switch, and BASELINE config 5 (mixed pool, vardiff, steady state).
 the native CPU scanner in place of the kernels (tests/test_bench_launcher.py);
 its JSON says so in ``data`` and ``rehearsal``.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -141,6 +147,11 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-rehearsal", action="store_true",
                     help="gloo + native CPU scanner instead of the GPU kernels (launcher / collective tests)")
     ap.add_argument("--cpu-nonces", type=int, default=1 << 12, help="rehearsal: nonces per variant per step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other section too (single, scrypt, x11, miner, comm, cpu, "
+                         "latency, node, pool); without it a run measures the SHA-256d headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed SHA-256d step returned (its hits) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -504,6 +515,8 @@ class Bench:
 
     def wanted(self, name: str) -> bool:
         a, cpu = self.args, self.cpu
+        if not a.full:  # a plain run is the headline alone
+            return False
         return {
             "single": a.single_midstate_headers > 0 and not cpu,
             "scrypt": (a.steps if a.scrypt_steps < 0 else a.scrypt_steps) > 0 and not cpu,
@@ -851,11 +864,13 @@ class Bench:
         # Re-verify every hit of the timed region on the CPU (full 256-bit compare), de-duplicated by (variant, nonce).
         found = verified = dups = outside = 0
         seen: set = set()
+        returned: list = []  # per timed step: (the slot's hit counter, its (nonce, variant) pairs)
         for hdrs, buf, lo, cnt in hits_log:
             host = buf.cpu().tolist()
             n = min(host[0] & 0xFFFFFFFF, search.cap)
             pairs = [(host[1 + 2 * i], host[2 + 2 * i]) for i in range(n)] if K > 1 else \
                 [(x, 0) for x in host[1 : 1 + n]]
+            returned.append((host[0] & 0xFFFFFFFF, [(nonce & 0xFFFFFFFF, vi) for nonce, vi in pairs]))
             for nonce, vi in pairs:
                 nonce &= 0xFFFFFFFF
                 found += 1
@@ -881,6 +896,33 @@ class Bench:
             "dups": dups, "outside": outside, "expected": expected, "z": z,
             "r2_hits": rows[0][3] if rows else 0,  # rank 0's R2 view of every rank's hit counts
         }
+        if args.dump_outputs:
+            self.dump_outputs(returned, int(r2_seen.item()))
+
+    def dump_outputs(self, returned: list, r2_total: int) -> None:
+        """--dump-outputs DIR: what the timed path handed back, as float64 .npy files (a u32 is exact in a float64).
+        The kernel appends hits to its slot in the order its waves find them, which differs from run to run, so every
+        list is written sorted; the synthetic job is fixed by --seed, so two builds run with the same arguments must
+        write the same files. At N > 1 each rank writes its own stripe's files (``.rank<r>`` in the name past rank 0).
+          hits       the last timed step's slot: one (nonce, variant) row per hit
+          hit_count  the last timed step's hit counter (it counts past the slot's capacity)
+          hits_timed every timed step's slot: (step, nonce, variant) rows
+          r2_hits    hits of every rank that reached this rank through R2 over the timed steps"""
+        import numpy as np
+
+        d = self.args.dump_outputs
+        os.makedirs(d, exist_ok=True)
+        tag = f".rank{self.rank}" if self.rank else ""
+        count, pairs = returned[-1] if returned else (0, [])
+        arrays = {
+            "hits": np.array(sorted(pairs), dtype=np.float64).reshape(-1, 2),
+            "hit_count": np.array([count], dtype=np.float64),
+            "hits_timed": np.array(sorted((i, n, v) for i, (_c, ps) in enumerate(returned) for n, v in ps)[:1 << 21],
+                                   dtype=np.float64).reshape(-1, 3),  # at most 48 MiB (the first 2^21 rows)
+            "r2_hits": np.array([r2_total], dtype=np.float64),
+        }
+        for name, a in arrays.items():
+            np.save(os.path.join(d, f"{name}{tag}.npy"), a)
 
     def single(self) -> None:
         """BASELINE config 2 verbatim: one fixed midstate, full 2^32 nonces per header."""

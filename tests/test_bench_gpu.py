@@ -24,7 +24,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--single-midstate-headers", "1", "--scrypt-steps", "2", "--x11-steps", "2",
+                          "--full", "--single-midstate-headers", "1", "--scrypt-steps", "2", "--x11-steps", "2",
                           "--miner-seconds", "0", "--no-latency", "--cpu-seconds", "0", "--node-seconds", "0",
                           "--pool-seconds", "0"], capture_output=True, text=True, timeout=220, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-4000:]

@@ -64,8 +64,8 @@ def test_world8_stuck_rank_in_preflight_prints_an_error_json():
 @pytest.mark.timeout(300)
 def test_stuck_node_section_keeps_the_full_json():
     """Rank 0 hangs in the node section: the section records its timeout and every earlier result is printed."""
-    res, took = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--cpu-seconds", "0.3",
-                       "--node-seconds", "3", "--section-timeouts", "node=12",
+    res, took = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--full", "--cpu-seconds",
+                       "0.3", "--node-seconds", "3", "--section-timeouts", "node=12",
                        env={"OTEDAMA_BENCH_FAULT": "stuck:0:node"}, timeout=200)
     assert res.returncode == 0, res.stderr[-3000:]
     d = _json(res)
@@ -203,8 +203,8 @@ def test_data_plane_probe_falls_back_together_and_still_measures(fault):
            "OTEDAMA_PROBE_TIMEOUT": "8"}
     if fault:
         env["OTEDAMA_BENCH_FAULT"] = fault
-    res, took = _bench("--gpus", "4", "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--cpu-seconds", "0",
-                       "--comm-ops", "20", env=env, timeout=240)
+    res, took = _bench("--gpus", "4", "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--full", "--cpu-seconds",
+                       "0", "--comm-ops", "20", env=env, timeout=240)
     assert res.returncode == 0, res.stderr[-3000:]
     d = _json(res)
     dp = d["preflight"]["data_plane"]
@@ -233,8 +233,8 @@ def test_probe_with_default_deadlines_fits_the_preflight_under_skew_and_a_hang()
     measured. --preflight-timeout 90 keeps the test short; the derivation is the same as at the default 240 s."""
     env = {"OTEDAMA_RCCL_MODULE": "loopback_rccl", "PYTHONPATH": os.path.join(ROOT, "tests"),
            "OTEDAMA_BENCH_FAULT": "slow:2:arrive,hang:1:probe", "OTEDAMA_FAULT_SLOW_S": "25"}
-    res, took = _bench("--gpus", "4", "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--cpu-seconds", "0",
-                       "--comm-ops", "10", "--preflight-timeout", "90", env=env, timeout=280)
+    res, took = _bench("--gpus", "4", "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--full", "--cpu-seconds",
+                       "0", "--comm-ops", "10", "--preflight-timeout", "90", env=env, timeout=280)
     assert res.returncode == 0, res.stderr[-3000:]
     d = _json(res)
     dp = d["preflight"]["data_plane"]
@@ -253,8 +253,8 @@ def test_a_rank_stuck_in_the_comm_section_costs_only_that_section():
     the native data plane's CPU stand-in."""
     env = {"OTEDAMA_RCCL_MODULE": "loopback_rccl", "PYTHONPATH": os.path.join(ROOT, "tests"),
            "OTEDAMA_BENCH_FAULT": "stuck:2:comm"}
-    res, took = _bench("--gpus", "4", "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--cpu-seconds", "0.3",
-                       "--comm-ops", "10", "--section-timeouts", "comm=24", env=env, timeout=280)
+    res, took = _bench("--gpus", "4", "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--full", "--cpu-seconds",
+                       "0.3", "--comm-ops", "10", "--section-timeouts", "comm=24", env=env, timeout=280)
     assert res.returncode == 0, res.stderr[-3000:]
     d = _json(res)
     assert d["value"] > 0 and d.line["summary"]["data_plane"] == "rccl-native"

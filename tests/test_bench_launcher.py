@@ -65,6 +65,47 @@ def test_single_rank_rehearsal_keeps_the_json_contract():
     assert "REHEARSAL" in d["data"]
 
 
+def test_plain_run_is_the_headline_alone_and_dumps_what_the_last_step_returned(tmp_path):
+    """Without --full a run measures the SHA-256d headline and nothing else (no other section starts, their keys are
+    null). --dump-outputs writes the last timed step's hits and every timed step's hits as float64 .npy: each row
+    verifies against hashlib under the run's target, the counts are the line's, and a second run with the same
+    arguments writes the same arrays."""
+    import hashlib
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    try:
+        import bench
+    finally:
+        sys.path.remove(ROOT)
+    from otedama_amd.ops import native
+    from otedama_amd.parallel import stripe_for
+
+    dumps = []
+    for name in ("a", "b"):
+        res = _bench("--steps", "3", "--warmup", "1", "--cpu-rehearsal", "--dump-outputs", str(tmp_path / name))
+        assert res.returncode == 0, res.stderr[-3000:]
+        d = _json(res)
+        assert set(d["sections"]) == {"preflight", "sha256d"} and d["errors"] is None
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["comm"] is None and d["cpu"] is None
+        assert d.line["summary"]["cfg1_cpu_1t_hps"] is None
+        assert sorted(os.listdir(tmp_path / name)) == ["hit_count.npy", "hits.npy", "hits_timed.npy", "r2_hits.npy"]
+        dumps.append({f[:-4]: np.load(tmp_path / name / f) for f in os.listdir(tmp_path / name)})
+    a, b = dumps
+    assert all(a[k].dtype == np.float64 and np.array_equal(a[k], b[k]) for k in a)
+    assert a["hits"].shape == (int(a["hit_count"][0]), 2) and len(a["hits"]) > 0
+    assert len(a["hits_timed"]) == d["hits_found"] == int(a["r2_hits"][0])
+    assert np.array_equal(a["hits_timed"][a["hits_timed"][:, 0] == 2][:, 1:], a["hits"])  # the last of 3 steps
+    # every row is a hit: the rehearsal's step i scans nonces [i % 2 * 4096, +4096) of variants 4 * (i // 2) .. + 3
+    N = native.require_native()
+    job, stripe = bench.synthetic_job(1), stripe_for(0, 1)
+    for step, nonce, vi in a["hits_timed"].astype(np.int64).tolist():
+        hdr = N.variant_header(job, stripe.start + (4 * (step // 2) + vi) * stripe.stride)[0]
+        h = hashlib.sha256(hashlib.sha256(hdr[:76] + nonce.to_bytes(4, "little")).digest()).digest()
+        assert int.from_bytes(h, "little") < 1 << 244 and (step % 2) * 4096 <= nonce < (step % 2 + 1) * 4096
+
+
 def test_refuses_more_gpus_than_visible():
     res = _bench("--gpus", "2", "--steps", "1", "--warmup", "0", env={"HIP_VISIBLE_DEVICES": "", "CUDA_VISIBLE_DEVICES": ""})
     assert res.returncode != 0
@@ -119,7 +160,8 @@ def test_driver_torchrun_invocation_on_the_native_data_plane():
     e.update(OTEDAMA_RCCL_MODULE="loopback_rccl", PYTHONPATH=os.path.join(ROOT, "tests"))
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), BENCH, "--gpus", "4",
-                          "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--cpu-seconds", "0", "--comm-ops", "20"],
+                          "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--full", "--cpu-seconds", "0", "--comm-ops",
+                          "20"],
                          capture_output=True, text=True, timeout=240, env=e, cwd=ROOT)
     res.detail = e["OTEDAMA_BENCH_DETAIL"]
     assert res.returncode == 0, res.stderr[-3000:]
@@ -146,7 +188,7 @@ def test_driver_torchrun_invocation_with_the_node_section():
     e.update(detail_env(tempfile.mkdtemp(prefix="otd-bench-"))[0])
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), BENCH, "--gpus", "4",
-                          "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--node-seconds", "3",
+                          "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--full", "--node-seconds", "3",
                           "--node-warmup", "2", "--cpu-seconds", "0"],
                          capture_output=True, text=True, timeout=360, env=e, cwd=ROOT)
     res.detail = e["OTEDAMA_BENCH_DETAIL"]
@@ -191,8 +233,8 @@ def test_node_section_json_contract(n):
     At world 8 the pool and CPU sections run too: the worst case of the printed line (missing #1: node
     objects for 3 algorithms x 8 ranks, the pool's) must still fit bench.LINE_CAP (checked in _json)."""
     extra = ("--pool-seconds", "3", "--cpu-seconds", "0.3") if n == 8 else ("--cpu-seconds", "0")
-    res = _bench("--gpus", str(n), "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--node-seconds", "3",
-                 "--node-warmup", "2", *extra, timeout=480)
+    res = _bench("--gpus", str(n), "--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--full", "--node-seconds",
+                 "3", "--node-warmup", "2", *extra, timeout=480)
     assert res.returncode == 0, res.stderr[-3000:]
     d = _json(res)
     s = d.line["summary"]
@@ -228,8 +270,8 @@ def test_pool_and_cpu_sections_json_contract():
     """BASELINE configs 1 and 5 in the bench JSON: the native CPU miner (single thread, all cores) and the mixed
     SHA-256d + scrypt pool with vardiff (here CPU miners for both algorithms), windowed once every worker converged
     (VERDICT r4 item 5), with the pool's flood capacity beside it."""
-    res = _bench("--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--pool-seconds", "3", "--cpu-seconds", "0.5",
-                 timeout=280)
+    res = _bench("--steps", "2", "--warmup", "1", "--cpu-rehearsal", "--full", "--pool-seconds", "3", "--cpu-seconds",
+                 "0.5", timeout=280)
     assert res.returncode == 0, res.stderr[-3000:]
     d = _json(res)
     assert d["cpu_single_thread_hashes_per_sec"] > 0 and d["cpu_all_cores_hashes_per_sec"] > 0

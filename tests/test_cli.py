@@ -509,7 +509,9 @@ def test_pool_config_errors(monkeypatch, args, needle):
 
 
 @pytest.mark.parametrize("addr,k,want", [("127.0.0.1:3336", 0, "127.0.0.1:3336"), ("127.0.0.1:3336", 2, "127.0.0.1:3338"),
-                                         ("127.0.0.1:0", 3, "127.0.0.1:0"), ("", 1, ""), ("[::1]:10", 1, "[::1]:11")])
+                                         ("127.0.0.1:0", 3, "127.0.0.1:0"), ("", 1, ""),
+                                         # an id of its own: one made from "[::1]" holds "::", the node id's separator
+                                         pytest.param("[::1]:10", 1, "[::1]:11", id="ipv6-bracketed")])
 def test_pool_port_bump(addr, k, want):
     assert pool_cmd._bump(addr, k) == want
 

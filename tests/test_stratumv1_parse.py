@@ -386,8 +386,11 @@ def test_strip_scheme_unknown(url):
         B.strip_scheme(url)
 
 
-@pytest.mark.parametrize("hp,want", [("pool:3333", ("pool", 3333)), ("pool", ("pool", 9)), ("[::1]:10", ("::1", 10)),
-                                     ("[::1]", ("::1", 9)), ("pool:3333/path", ("pool", 3333))])
+# the IPv6 cases carry ids of their own: an id made from "[::1]" holds "::", the separator of a test's node id
+@pytest.mark.parametrize("hp,want", [("pool:3333", ("pool", 3333)), ("pool", ("pool", 9)),
+                                     pytest.param("[::1]:10", ("::1", 10), id="ipv6-with-port"),
+                                     pytest.param("[::1]", ("::1", 9), id="ipv6-no-port"),
+                                     ("pool:3333/path", ("pool", 3333))])
 def test_split_host_port(hp, want):
     assert B.split_host_port(hp, 9) == want
 
