@@ -11,6 +11,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <thread>
+#include <tuple>
 
 #include "otedama/aead.h"
 #include "otedama/job.h"
@@ -19,30 +20,13 @@
 #include "otedama/sha256.h"
 #include "otedama/sv2_frame.h"
 #include "otedama/clock_bounds.h"
+#include "otedama/launch_plan.h"
+#include "otedama/search_launch.h"
 #include "otedama/work_queue.h"
 #include "otedama/x11.h"
 
 namespace py = pybind11;
 using namespace otedama;
-
-namespace otedama {
-void py_launch_sha256d(const Sha256dParams& p, uint32_t base, uint64_t count, uintptr_t out, uint32_t cap, int grid,
-                       uintptr_t stream);
-void py_launch_sha256d_k(const Sha256dParamsK& p, uint32_t base, uint64_t count, uintptr_t out, uint32_t cap, int grid,
-                         uintptr_t stream);
-void py_launch_sha256d_v(const Sha256dParamsV& p, uintptr_t vars, uint32_t base, uint64_t count, uintptr_t out,
-                         uint32_t cap, int grid, uintptr_t stream, int block, int chains);
-void py_launch_scrypt(const ScryptParams& p, uint32_t base, uint32_t count, uintptr_t xbuf, uintptr_t scratch, int gap,
-                      uintptr_t out, uint32_t cap, int grid, uintptr_t stream);
-void py_launch_x11_stage(const X11Params& p, int stage, uint32_t base, uintptr_t H, uint32_t stride, uint32_t n,
-                         uintptr_t out, uint32_t cap, uintptr_t stream);
-void py_launch_x11(const X11Params& p, uint32_t base, uintptr_t H, uint32_t stride, uint32_t n, uintptr_t out,
-                   uint32_t cap, uintptr_t stream);
-uint64_t scrypt_scratch_bytes(int grid, int gap);
-int gpu_device_count();
-std::string gpu_arch_name(int device);
-int gpu_cu_count(int device);
-}  // namespace otedama
 
 namespace {
 
@@ -226,6 +210,43 @@ PYBIND11_MODULE(_native, m) {
     for (const auto& s : samples) out.push_back(cb.add(s.first, s.second));
     return out;
   });
+  // Test hook: the miner's search-plan rules (otedama/launch_plan.h), each from its own arguments: the normalised
+  // batch, the launch cap of a target, the SHA-256d layout of a run, the CU mask of a reservation list.
+  m.def("_launch_plan_rules", [](uint64_t batch_nonces, uint32_t target_hi, bool capped, int sha_variants, int run,
+                                 const std::string& reserve_cus, int ncu) {
+    const ShaLayout lay = pick_layout(sha_variants, run);
+    const CuMask cm = parse_reserved_cus(reserve_cus.c_str(), ncu);
+    py::dict d;
+    d["batch"] = normalize_batch(batch_nonces);
+    d["cap"] = launch_cap_hashes(target_hi, capped);
+    d["layout"] = py::make_tuple(lay.nvar, lay.use_v);
+    d["cu_mask"] = cm.words;
+    d["reserved"] = cm.reserved;
+    return d;
+  }, py::arg("batch_nonces") = 0, py::arg("target_hi") = 0, py::arg("capped") = true, py::arg("sha_variants") = 1,
+     py::arg("run") = 1, py::arg("reserve_cus") = "", py::arg("ncu") = 256);
+  // Test hook: the miner's cursor walked over launches of one kind ("scrypt", "x11", "v", "k", "single") from
+  // nonce offset `start` until the stripe position moves (or `max_launches`): every launch's (base, count,
+  // variant_next) and the stripe position reached.
+  m.def("_launch_plan_walk", [](const std::string& kind, uint64_t batch, uint64_t cap, int nvar, uint64_t lanes,
+                                uint64_t start, size_t max_launches, uint64_t variant_start, uint64_t variant_stride) {
+    const LaunchKind lk = kind == "scrypt" ? LaunchKind::kScrypt : kind == "x11" ? LaunchKind::kX11
+                        : kind == "v" ? LaunchKind::kVersionParallel : kind == "k" ? LaunchKind::kVariantK
+                        : kind == "single" ? LaunchKind::kSingle
+                        : throw std::invalid_argument("kind: scrypt, x11, v, k or single");
+    if (start >= kNonceSpace) throw std::invalid_argument("start must be below 2^32");
+    SearchCursor c;
+    c.nonce_off = start;
+    std::vector<std::tuple<uint64_t, uint64_t, uint64_t>> launches;
+    while (c.k == 0 && launches.size() < max_launches) {
+      const uint64_t base = c.nonce_off, count = launch_count(lk, batch, cap, nvar, lanes, c.nonce_off);
+      c.advance(count, nvar);
+      launches.emplace_back(base, count, c.variant_next(variant_start, variant_stride, nvar));
+    }
+    return py::make_tuple(launches, c.k);
+  }, py::arg("kind"), py::arg("batch"), py::arg("cap"), py::arg("nvar") = 1, py::arg("lanes") = 0,
+     py::arg("start") = 0, py::arg("max_launches") = size_t(1) << 20, py::arg("variant_start") = 0,
+     py::arg("variant_stride") = 1);
   // Test hook: the scrypt verifier's bounded queue (BoundedWorkQueue) flooded by a producer that never waits, with
   // a consumer hashing every item on the host. batch > 1 takes up to that many items per pop_many and hashes them in
   // one scrypt_1024_1_1_batch pass, as the GPU miner's verifier does (16); batch 1 pops and hashes one at a time.

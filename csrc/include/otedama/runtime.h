@@ -186,17 +186,12 @@ class GpuMiner : public MinerBase {
   void start() override;
   void stop() override;
  private:
+  struct Run;  // the device thread's state and HIP resources (gpu_miner.hip)
   void loop();
   int device_;
   uint64_t batch_;
   int grid_;
-  int sha_k_;
-  bool sha_v_;   // version-parallel kernel enabled
-  bool sha_v2_;  // two-chain version-parallel kernel enabled (tried first)
-  int grid_k_ = 0;
-  int grid_v_ = 0;
-  int grid_v2_ = 0;
-  double rt_offset_ = 0;  // host monotonic seconds at device realtime 0 (s_memrealtime, 100 MHz)
+  int sha_variants_;  // as given; otedama/launch_plan.h (pick_layout) turns it into a kernel layout per stripe group
   std::thread th_;
 };
 

@@ -1,0 +1,58 @@
+// Launch entry points of the gfx950 search kernels (csrc/kernels/*.hip) and the device queries, declared once for
+// the files that define them, the GPU miner and the Python bindings. The X11 stage launchers are in
+// otedama/x11_launch.h. The first part is plain C++ (bindings.cpp is compiled by the host compiler); the launches
+// that take a hipStream_t are visible to HIP translation units only.
+#pragma once
+#include <cstdint>
+#include <string>
+
+#include "otedama/hitsink.h"
+#include "otedama/job.h"
+
+namespace otedama {
+
+// Scratchpad bytes for `grid` ROMix blocks of 256 lane slots at lookup gap `gap` (scrypt_search.hip).
+uint64_t scrypt_scratch_bytes(int grid, int gap);
+
+// Device queries (gpu_miner.hip): 0 / "" when the runtime cannot answer.
+int gpu_device_count();
+std::string gpu_arch_name(int device);
+int gpu_cu_count(int device);
+
+// Launches for the Python ops layer (gpu_miner.hip; torch-owned buffers and streams): pointers and the stream arrive
+// as integers, a HIP error is thrown as std::runtime_error. Hits go to the legacy device-memory slots after out[0];
+// no abort word.
+void py_launch_sha256d(const Sha256dParams& p, uint32_t base, uint64_t count, uintptr_t out, uint32_t cap, int grid,
+                       uintptr_t stream);
+void py_launch_sha256d_k(const Sha256dParamsK& p, uint32_t base, uint64_t count, uintptr_t out, uint32_t cap, int grid,
+                         uintptr_t stream);
+void py_launch_sha256d_v(const Sha256dParamsV& p, uintptr_t vars, uint32_t base, uint64_t count, uintptr_t out,
+                         uint32_t cap, int grid, uintptr_t stream, int block, int chains);
+void py_launch_scrypt(const ScryptParams& p, uint32_t base, uint32_t count, uintptr_t xbuf, uintptr_t scratch, int gap,
+                      uintptr_t out, uint32_t cap, int grid, uintptr_t stream);
+void py_launch_x11_stage(const X11Params& p, int stage, uint32_t base, uintptr_t H, uint32_t stride, uint32_t n,
+                         uintptr_t out, uint32_t cap, uintptr_t stream);
+void py_launch_x11(const X11Params& p, uint32_t base, uintptr_t H, uint32_t stride, uint32_t n, uintptr_t out,
+                   uint32_t cap, uintptr_t stream);
+
+}  // namespace otedama
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+
+namespace otedama {
+
+// `count` nonces from `base` on `grid` blocks of 256 (sha256d_search.hip, sha256d_search_v.hip); hits go to `sink`.
+hipError_t launch_sha256d_search(const Sha256dParams& p, uint32_t base, uint64_t count, const HitSink& sink, int grid,
+                                 hipStream_t stream);
+hipError_t launch_sha256d_search_k(const Sha256dParamsK& p, uint32_t base, uint64_t count, const HitSink& sink,
+                                   int grid, hipStream_t stream);
+hipError_t launch_sha256d_search_v(const Sha256dParamsV& p, const Sha256dVariant* vars, uint32_t base, uint64_t count,
+                                   const HitSink& sink, int grid, hipStream_t stream, int block = 256, int chains = 1);
+
+// xbuf: count * 128 bytes. scratch: scrypt_scratch_bytes(grid, gap) (scrypt_search.hip).
+hipError_t launch_scrypt_search(const ScryptParams& p, uint32_t base, uint32_t count, void* xbuf, void* scratch,
+                                int gap, const HitSink& sink, int grid, hipStream_t stream);
+
+}  // namespace otedama
+#endif

@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "otedama/job.h"
+#include "otedama/search_launch.h"
 
 namespace {
 

@@ -23,6 +23,7 @@
 #include "cdna_bitops.h"
 #include "hitsink_dev.h"
 #include "otedama/job.h"
+#include "otedama/search_launch.h"
 
 namespace {
 

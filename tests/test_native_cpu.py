@@ -330,6 +330,120 @@ def test_clock_bounds_track_the_window_minimum():
     assert N._clock_bounds(2.0, [(0.0, 5.0)]) == [5.0]
 
 
+# ---- the GPU miner's search plan (otedama/launch_plan.h): which nonces a launch covers. Expected values come from
+# the rules as documented, not from running the code.
+
+NONCES = 1 << 32
+NO_CAP = 1 << 40
+
+
+@pytest.mark.parametrize("target_hi,capped,want", [
+    (3999, True, 1 << 29),        # 512 expected candidates allowed: 512 * 2^32 / 4000 ~ 5.50e8, next power of two below
+    (15999, True, 1 << 27),       # 512 * 2^32 / 16000 ~ 1.37e8
+    (255, True, 1 << 33),         # 512 * 2^32 / 256 = 2^33: a 2^32 batch is left alone
+    (0xFFFFFFFF, True, 1 << 22),  # every hash a candidate: the floor (launch overhead)
+    (0, True, NO_CAP),            # 512 * 2^32 / 1 = 2^41 is above the "no cut" value
+    (3999, False, NO_CAP),
+    (0xFFFFFFFF, False, NO_CAP),
+])
+def test_launch_cap_follows_the_share_target(target_hi, capped, want):
+    """Launches are cut to powers of two until the expected candidates (hashes * (target_hi + 1) / 2^32) fit in an
+    eighth of the 4096-record hit ring. 3999 and 15999 are the targets of the GPU tests
+    test_launches_are_sized_from_the_share_target... and test_ring_overflow_is_counted_exactly."""
+    assert N._launch_plan_rules(target_hi=target_hi, capped=capped)["cap"] == want
+
+
+@pytest.mark.parametrize("given,want", [(0, 1 << 30), (1 << 33, 1 << 30), (3 << 20, 1 << 21), (1 << 29, 1 << 29),
+                                        (1 << 32, 1 << 32), (1, 1)])
+def test_batch_is_normalised_to_a_divisor_of_the_nonce_range(given, want):
+    assert N._launch_plan_rules(batch_nonces=given)["batch"] == want
+
+
+@pytest.mark.parametrize("sha_variants,run,want", [
+    (128, 128, (128, True)), (128, 127, (64, True)), (128, 63, (16, False)), (128, 5, (4, False)),
+    (128, 1, (1, False)), (64, 200, (64, True)), (8, 200, (8, False)), (8, 7, (6, False)), (1, 200, (1, False)),
+    (0, 200, (1, False)), (0, 1, (1, False)), (-3, 64, (1, False)),
+    (40, 200, (16, False)),  # 17..63 clamp to K = 16 and enable no version-parallel kernel
+])
+def test_sha256d_layout_falls_back_128_64_k(sha_variants, run, want):
+    """(variants per launch, version-parallel kernel?) for a miner configured with sha_variants when `run`
+    consecutive stripe positions share block 2; K is rounded down to an instantiated one."""
+    assert N._launch_plan_rules(sha_variants=sha_variants, run=run)["layout"] == want
+
+
+def test_reserved_cu_mask():
+    def mask(spec, ncu=256):
+        r = N._launch_plan_rules(reserve_cus=spec, ncu=ncu)
+        return r["cu_mask"], r["reserved"]
+
+    full = [0xFFFFFFFF] * 8
+    assert mask("0,32") == ([0xFFFFFFFE, 0xFFFFFFFE] + full[2:], 2)
+    assert mask("0,0") == ([0xFFFFFFFE] + full[1:], 1)  # a repeat is counted once
+    assert mask("300") == (full, 0)                     # out of range
+    assert mask("") == (full, 0)
+    assert mask("7,x") == ([0xFFFFFF7F] + full[1:], 1)  # parsing stops at the junk
+    assert mask("7,x,9") == mask("7,x")
+    words, reserved = mask("303", ncu=304)               # 304 CUs: ten words, sixteen bits in the last
+    assert len(words) == 10 and words[:9] == [0xFFFFFFFF] * 9 and words[9] == (1 << 16) - 1 - (1 << 15)
+    assert reserved == 1 and mask("", ncu=304)[0][9] == (1 << 16) - 1
+
+
+# (kind, nvar, lanes, batch) of every launch family; 622592 = 304 CUs * 16 blocks * 256 lanes, halved: not a power
+# of two, so the last launch of the range is short
+_TILINGS = ([("single", 1, 0, 1 << 29)]
+            + [("v", nvar, 0, batch) for nvar in (64, 128) for batch in (1 << 29, 1 << 32)]
+            + [("k", k, 0, 1 << 30) for k in (2, 3, 4, 6, 8, 12, 16)]
+            + [("x11", 1, 1 << 23, 1 << 30)]
+            + [("scrypt", 1, lanes, 1 << 30) for lanes in (1 << 20, 1 << 19, 622592)])
+
+
+def _hash_bound(kind, nvar, lanes, batch, cap):
+    """Most hashes one launch may hold. scrypt / X11 launches are sized by their buffers, not the batch."""
+    limit = min(lanes, cap) if kind in ("scrypt", "x11") else min(batch, cap)
+    return limit * 3 // 2 if kind == "k" and nvar in (3, 6, 12) else limit
+
+
+# caps: none; 2^27 (test_ring_overflow_is_counted_exactly's target); 2^22, the floor, below every batch and the X11
+# buffer. The scrypt buffers are smaller than any cap a target gives, so scrypt also gets 2^18 to see a launch cut.
+_TILING_CASES = [t + (cap,) for t in _TILINGS
+                 for cap in (NO_CAP, 1 << 27, 1 << 22) + ((1 << 18,) if t[0] == "scrypt" else ())]
+
+
+@pytest.mark.parametrize("kind,nvar,lanes,batch,cap", _TILING_CASES,
+                         ids=[f"{t[0]}-{t[1]}-{t[2]}-b{t[3].bit_length() - 1}-cap{t[4].bit_length() - 1}"
+                              for t in _TILING_CASES])
+def test_launches_tile_the_nonce_range_exactly(kind, nvar, lanes, batch, cap):
+    """Walking the cursor from reset() until the stripe position moves: every launch holds at least one nonce, the
+    bases are contiguous from 0, the counts sum to exactly 2^32 (nothing skipped, nothing searched twice), the stripe
+    position moved by the group's width, and variant_next names the group after the current one throughout. Hashes
+    per launch (count * nvar) stay within the cap, except that the K-variant kernel at K = 3, 6, 12 divides by the
+    largest power of two <= K and so holds 1.5x (today's behaviour, pinned here)."""
+    launches, k = N._launch_plan_walk(kind, batch, cap, nvar=nvar, lanes=lanes, variant_start=5, variant_stride=3)
+    at = 0
+    for base, count, variant_next in launches:
+        assert count >= 1 and base == at, (base, count, at)
+        assert count * nvar <= _hash_bound(kind, nvar, lanes, batch, cap), (base, count)
+        assert variant_next == 5 + 3 * nvar
+        at += count
+    assert at == NONCES and k == nvar
+    if kind == "scrypt" and lanes == 622592 and cap > lanes:
+        assert launches[-1][1] == NONCES % lanes != 0  # the short last launch
+
+
+@pytest.mark.parametrize("kind,nvar,lanes", [("single", 1, 0), ("v", 128, 0), ("v", 64, 0), ("k", 6, 0), ("k", 16, 0),
+                                             ("x11", 1, 1 << 23), ("scrypt", 1, 1 << 20)])
+def test_a_batch_of_one_nonce_still_advances(kind, nvar, lanes):
+    """batch = 1 (2^32 launches per group: walked at both ends of the range rather than through it). A SHA-256d
+    launch then holds one nonce per variant, never zero; scrypt and X11 ignore the batch setting. The last launch of
+    the range moves the stripe position."""
+    own = lanes or 1  # nonces per launch
+    first, k = N._launch_plan_walk(kind, 1, NO_CAP, nvar=nvar, lanes=lanes, max_launches=3)
+    assert first == [(i * own, own, nvar) for i in range(3)] and k == 0
+    last, k = N._launch_plan_walk(kind, 1, NO_CAP, nvar=nvar, lanes=lanes, start=NONCES - 3 * own)
+    assert [(b, c) for b, c, _ in last] == [(NONCES - (3 - i) * own, own) for i in range(3)] and k == nvar
+    assert last[-1][2] == nvar  # the group is done and the next one not started: variant_next is its first variant
+
+
 @pytest.mark.parametrize("lanes", [1, 2, 3, 4, 16])
 def test_cpu_scan_lanes_agree(lanes):
     """Every interleave width of the CPU scan finds the same hits (genesis nonce at its target; an easy target over

@@ -15,6 +15,8 @@
 //  3. No duplicates: a (work, extranonce2, version, ntime, nonce) tuple is never emitted twice, even
 //     across re-issues of the same work and pause/resume (the cursor must not restart).
 //  4. AEAD round trip + tamper rejection and scrypt/HMAC/PBKDF2 on odd lengths (ASan coverage).
+//  5. The GPU miner's search plan (otedama/launch_plan.h): launch caps, and launches of every kernel family tile
+//     the 2^32 nonce range exactly (UBSan coverage of its shifts and narrowing casts).
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -30,6 +32,7 @@
 #include <vector>
 
 #include "otedama/aead.h"
+#include "otedama/launch_plan.h"
 #include "otedama/runtime.h"
 #include "otedama/sha256.h"
 
@@ -242,8 +245,71 @@ static void test_crypto_memory() {
   }
 }
 
+// The GPU miner's search plan (otedama/launch_plan.h) under UBSan: the cap table and the cursor walked over every
+// launch family until the stripe position moves (the same cases as tests/test_native_cpu.py).
+static void walk_plan(LaunchKind kind, uint64_t batch, uint64_t cap, int nvar, uint64_t lanes) {
+  const bool buffered = kind == LaunchKind::kScrypt || kind == LaunchKind::kX11;
+  uint64_t bound = buffered ? std::min(lanes, cap) : std::min(batch, cap);
+  if (kind == LaunchKind::kVariantK && (nvar == 3 || nvar == 6 || nvar == 12)) bound = bound * 3 / 2;
+  SearchCursor c;
+  c.reset();
+  uint64_t at = 0, launches = 0;
+  while (c.k == 0 && launches < (1ull << 22)) {
+    const uint64_t count = launch_count(kind, batch, cap, nvar, lanes, c.nonce_off);
+    CHECK(count >= 1 && c.nonce_off == at, "plan: launch %llu at %llu holds %llu nonces, expected base %llu",
+          (unsigned long long)launches, (unsigned long long)c.nonce_off, (unsigned long long)count,
+          (unsigned long long)at);
+    CHECK(count * uint64_t(nvar) <= bound, "plan: launch of %llu x %d hashes over its bound %llu",
+          (unsigned long long)count, nvar, (unsigned long long)bound);
+    if (count < 1) return;
+    at += count;
+    ++launches;
+    c.advance(count, nvar);
+    CHECK(c.variant_next(5, 3, nvar) == 5 + 3 * uint64_t(nvar), "plan: variant_next");
+  }
+  CHECK(at == kNonceSpace && c.k == uint64_t(nvar) && c.nonce_off == 0,
+        "plan: kind %d nvar %d batch %llu cap %llu covered %llu nonces, k = %llu", int(kind), nvar,
+        (unsigned long long)batch, (unsigned long long)cap, (unsigned long long)at, (unsigned long long)c.k);
+}
+
+static void test_launch_plan() {
+  const struct { uint32_t target_hi; bool capped; uint64_t want; } caps[] = {
+      {3999, true, 1ull << 29}, {15999, true, 1ull << 27}, {255, true, 1ull << 33}, {0xFFFFFFFFu, true, 1ull << 22},
+      {0, true, 1ull << 40},    {3999, false, 1ull << 40}, {0xFFFFFFFFu, false, 1ull << 40}};
+  for (const auto& c : caps)
+    CHECK(launch_cap_hashes(c.target_hi, c.capped) == c.want, "plan: cap for target_hi %u", c.target_hi);
+  CHECK(normalize_batch(0) == 1ull << 30 && normalize_batch(1ull << 33) == 1ull << 30 &&
+        normalize_batch(3ull << 20) == 1ull << 21 && normalize_batch(1ull << 29) == 1ull << 29, "plan: batch");
+  for (uint64_t cap : {1ull << 40, 1ull << 27, 1ull << 22}) {
+    walk_plan(LaunchKind::kSingle, 1ull << 29, cap, 1, 0);
+    for (int nvar : {64, 128})
+      for (uint64_t batch : {1ull << 29, 1ull << 32}) walk_plan(LaunchKind::kVersionParallel, batch, cap, nvar, 0);
+    for (int k : {2, 3, 4, 6, 8, 12, 16}) walk_plan(LaunchKind::kVariantK, 1ull << 30, cap, k, 0);
+    walk_plan(LaunchKind::kX11, 1ull << 30, cap, 1, 1ull << 23);
+    for (uint64_t lanes : {1ull << 20, 1ull << 19, 622592ull})
+      walk_plan(LaunchKind::kScrypt, 1ull << 30, cap, 1, lanes);
+  }
+  for (uint64_t lanes : {1ull << 20, 1ull << 19, 622592ull})
+    walk_plan(LaunchKind::kScrypt, 1ull << 30, 1ull << 18, 1, lanes);
+  // batch = 1: one nonce per variant, never zero, and the last launch of the range moves the stripe position
+  for (int nvar : {1, 6, 128}) {
+    const LaunchKind kind = nvar == 1 ? LaunchKind::kSingle : nvar == 6 ? LaunchKind::kVariantK
+                                                                         : LaunchKind::kVersionParallel;
+    SearchCursor c;
+    c.nonce_off = kNonceSpace - 1;
+    CHECK(launch_count(kind, 1, 1ull << 40, nvar, 0, 0) == 1, "plan: batch 1 at 0");
+    const uint64_t count = launch_count(kind, 1, 1ull << 40, nvar, 0, c.nonce_off);
+    c.advance(count, nvar);
+    CHECK(count == 1 && c.k == uint64_t(nvar) && c.nonce_off == 0, "plan: batch 1 at the end of the range");
+  }
+  const CuMask cm = parse_reserved_cus("0,32,0,400,7,x,9", 304);
+  CHECK(cm.reserved == 3 && cm.words.size() == 10 && cm.words[0] == 0xFFFFFF7Eu && cm.words[1] == 0xFFFFFFFEu &&
+        cm.words[9] == 0xFFFFu, "plan: cu mask");
+}
+
 int main(int argc, char** argv) {
   const double seconds = argc > 1 ? std::atof(argv[1]) : 4.0;
+  test_launch_plan();
   test_share_queue();
   test_job_epochs(4, seconds);
   test_crypto_memory();
