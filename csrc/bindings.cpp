@@ -501,6 +501,26 @@ PYBIND11_MODULE(_native, m) {
   }, py::arg("params"), py::arg("base"), py::arg("H"), py::arg("stride"), py::arg("n"), py::arg("out") = 0,
      py::arg("cap") = 0, py::arg("stream") = 0);
 
+  // Digest ops: n unrelated 80-byte headers (device pointer, densely packed) -> n 32-byte digests.
+  m.def("launch_sha256d_digest", [](uintptr_t headers, uint32_t n, uintptr_t out, uintptr_t stream) {
+    if (headers == 0 || out == 0 || n == 0) throw std::invalid_argument("need headers != 0, out != 0, n > 0");
+    py_launch_sha256d_digest(headers, n, out, stream);
+  }, py::arg("headers"), py::arg("n"), py::arg("out"), py::arg("stream") = 0);
+  m.def("launch_scrypt_digest", [](uintptr_t headers, uint32_t n, uintptr_t xbuf, uintptr_t scratch, int gap,
+                                   uintptr_t out, int grid, uintptr_t stream) {
+    if (headers == 0 || out == 0 || xbuf == 0 || scratch == 0 || n == 0 || grid <= 0)
+      throw std::invalid_argument("bad launch args");
+    if (uint64_t(n) > uint64_t(grid) * 256u) throw std::invalid_argument("n must be at most grid * 256");
+    py_launch_scrypt_digest(headers, n, xbuf, scratch, gap, out, grid, stream);
+  }, py::arg("headers"), py::arg("n"), py::arg("xbuf"), py::arg("scratch"), py::arg("gap"), py::arg("out"),
+     py::arg("grid"), py::arg("stream") = 0);
+  m.def("launch_x11_digest", [](uintptr_t headers, uintptr_t H, uint32_t stride, uint32_t n, uintptr_t out,
+                                uintptr_t stream) {
+    if (headers == 0 || out == 0 || H == 0 || n == 0 || stride < n)
+      throw std::invalid_argument("need headers, H, out != 0, n > 0, stride >= n");
+    py_launch_x11_digest(headers, H, stride, n, out, stream);
+  }, py::arg("headers"), py::arg("H"), py::arg("stride"), py::arg("n"), py::arg("out"), py::arg("stream") = 0);
+
   py::class_<MinerBase, std::shared_ptr<MinerBase>>(m, "Miner")
       .def("start", &MinerBase::start, py::call_guard<py::gil_scoped_release>())
       .def("stop", &MinerBase::stop, py::call_guard<py::gil_scoped_release>())

@@ -35,6 +35,14 @@ void py_launch_x11_stage(const X11Params& p, int stage, uint32_t base, uintptr_t
 void py_launch_x11(const X11Params& p, uint32_t base, uintptr_t H, uint32_t stride, uint32_t n, uintptr_t out,
                    uint32_t cap, uintptr_t stream);
 
+// Digest ops (digest_batch.hip): n unrelated 80-byte headers at headers + 80 * i -> n digests at out + 32 * i, in
+// the byte order PowAlgorithm.hash returns. Same conventions as above; both arrays must be 16-byte aligned.
+void py_launch_sha256d_digest(uintptr_t headers, uint32_t n, uintptr_t out, uintptr_t stream);
+void py_launch_scrypt_digest(uintptr_t headers, uint32_t n, uintptr_t xbuf, uintptr_t scratch, int gap, uintptr_t out,
+                             int grid, uintptr_t stream);
+void py_launch_x11_digest(uintptr_t headers, uintptr_t H, uint32_t stride, uint32_t n, uintptr_t out,
+                          uintptr_t stream);
+
 }  // namespace otedama
 
 #ifdef __HIPCC__
@@ -53,6 +61,20 @@ hipError_t launch_sha256d_search_v(const Sha256dParamsV& p, const Sha256dVariant
 // xbuf: count * 128 bytes. scratch: scrypt_scratch_bytes(grid, gap) (scrypt_search.hip).
 hipError_t launch_scrypt_search(const ScryptParams& p, uint32_t base, uint32_t count, void* xbuf, void* scratch,
                                 int gap, const HitSink& sink, int grid, hipStream_t stream);
+
+// The ROMix launch(es) of launch_scrypt_search alone, over the `count` PBKDF2-in states in xbuf (scrypt_search.hip).
+hipError_t launch_scrypt_romix(uint32_t count, uint4* xbuf, uint4* scratch, int gap, const HitSink& sink, int grid,
+                               hipStream_t stream);
+
+// Digests of n unrelated headers (layout above). Each returns hipErrorInvalidValue, before launching anything, for
+// n == 0, n above the stated capacity, a null pointer or a header / digest array that is not 16-byte aligned.
+hipError_t launch_sha256d_digest(const uint8_t* headers, uint32_t n, uint8_t* out, hipStream_t s);
+// xbuf: grid * 256 * 128 bytes. scratch: scrypt_scratch_bytes(grid, gap). One header per lane slot.
+hipError_t launch_scrypt_digest(const uint8_t* headers, uint32_t n, void* xbuf, void* scratch, int gap,
+                                uint8_t* out, int grid, hipStream_t s);   // n <= grid * 256
+// H: 8 * stride u64, the stage planes of the X11 chain (otedama/x11_launch.h).
+hipError_t launch_x11_digest(const uint8_t* headers, uint64_t* H, uint32_t stride, uint32_t n, uint8_t* out,
+                             hipStream_t s);                              // n <= stride
 
 }  // namespace otedama
 #endif

@@ -19,4 +19,7 @@ hipError_t x11_launch_stage(int stage, const X11Params& p, uint32_t base, uint64
                             const HitSink* sink, hipStream_t s);
 hipError_t x11_launch_chain(const X11Params& p, uint32_t base, uint64_t* H, uint32_t stride, uint32_t n,
                             const HitSink* sink, hipStream_t s);
+// Stage 0 over n unrelated 80-byte headers (densely packed, 16-byte aligned) instead of one header and a nonce
+// range: header k fills the same planes as nonce base + k does above (the digest op, digest_batch.hip).
+hipError_t x11_launch_blake_hdr(const uint8_t* headers, uint64_t* H, uint32_t stride, uint32_t n, hipStream_t s);
 }  // namespace otedama

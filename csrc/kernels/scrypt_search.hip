@@ -20,6 +20,7 @@
 
 #include "cdna_bitops.h"
 #include "hitsink_dev.h"
+#include "scrypt_pbkdf_dev.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -29,8 +30,7 @@
 namespace {
 
 using namespace otedama_dev;
-
-__device__ __forceinline__ uint32_t bswap(uint32_t x) { return __builtin_bswap32(x); }
+using namespace otedama_dev::scryptk;
 
 __device__ __forceinline__ void salsa20_8(uint32_t B[16]) {
   uint32_t x0 = B[0], x1 = B[1], x2 = B[2], x3 = B[3], x4 = B[4], x5 = B[5], x6 = B[6], x7 = B[7];
@@ -58,117 +58,6 @@ __device__ __forceinline__ void blockmix(uint32_t X[32]) {
 #pragma unroll
   for (int k = 0; k < 16; ++k) X[16 + k] ^= X[k];
   salsa20_8(X + 16);
-}
-
-__device__ __forceinline__ void store_entry(uint4* __restrict__ dst, const uint32_t X[32]) {
-#pragma unroll
-  for (int q = 0; q < 8; ++q) dst[q] = make_uint4(X[4 * q], X[4 * q + 1], X[4 * q + 2], X[4 * q + 3]);
-}
-__device__ __forceinline__ void load_entry(const uint4* __restrict__ src, uint32_t T[32]) {
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const uint4 v = src[q];
-    T[4 * q] = v.x; T[4 * q + 1] = v.y; T[4 * q + 2] = v.z; T[4 * q + 3] = v.w;
-  }
-}
-
-// HMAC-SHA256 pad states for key K' (8 words).
-__device__ __forceinline__ void hmac_states(const uint32_t key[8], uint32_t istate[8], uint32_t ostate[8]) {
-  uint32_t blk[16];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) blk[i] = key[i] ^ 0x36363636u;
-#pragma unroll
-  for (int i = 8; i < 16; ++i) blk[i] = 0x36363636u;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) istate[i] = kSha256IVd[i];
-  sha256_compress(istate, blk);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) blk[i] = key[i] ^ 0x5c5c5c5cu;
-#pragma unroll
-  for (int i = 8; i < 16; ++i) blk[i] = 0x5c5c5c5cu;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) ostate[i] = kSha256IVd[i];
-  sha256_compress(ostate, blk);
-}
-
-// Outer HMAC step: H(opad-state || digest) with fixed padding (768-bit message).
-__device__ __forceinline__ void hmac_outer(const uint32_t ostate[8], const uint32_t digest[8], uint32_t out[8]) {
-  uint32_t blk[16];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) blk[i] = digest[i];
-  blk[8] = 0x80000000u;
-#pragma unroll
-  for (int i = 9; i < 15; ++i) blk[i] = 0u;
-  blk[15] = 768u;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) out[i] = ostate[i];
-  sha256_compress(out, blk);
-}
-
-// Stage 1: PBKDF2 #1 for `nonce` -> X[32] (LE words of the 128-byte B).
-__device__ __forceinline__ void scrypt_pbkdf_in(const otedama::ScryptParams& p, uint32_t nonce, uint32_t X[32]) {
-  // K' = SHA-256(header80) (key longer than the block size).
-  uint32_t hdrbe[20];
-#pragma unroll
-  for (int i = 0; i < 19; ++i) hdrbe[i] = bswap(p.hdr[i]);
-  hdrbe[19] = bswap(nonce);
-  uint32_t key[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) key[i] = p.hmid[i];
-  {
-    uint32_t blk[16] = {hdrbe[16], hdrbe[17], hdrbe[18], hdrbe[19], 0x80000000u, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 640u};
-    sha256_compress(key, blk);
-  }
-  uint32_t istate[8], ostate[8];
-  hmac_states(key, istate, ostate);
-  // salt = header80, 4 blocks of 32 bytes.
-  uint32_t ist2[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) ist2[i] = istate[i];
-  sha256_compress(ist2, hdrbe);  // header bytes 0..63
-#pragma unroll
-  for (int blkno = 1; blkno <= 4; ++blkno) {
-    uint32_t st[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st[i] = ist2[i];
-    uint32_t blk[16] = {hdrbe[16], hdrbe[17], hdrbe[18], hdrbe[19], uint32_t(blkno), 0x80000000u,
-                        0, 0, 0, 0, 0, 0, 0, 0, 0, (64u + 84u) * 8u};
-    sha256_compress(st, blk);
-    uint32_t t[8];
-    hmac_outer(ostate, st, t);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) X[8 * (blkno - 1) + i] = bswap(t[i]);
-  }
-}
-
-// Stage 3: PBKDF2 #2 over X (salt = X || INT(1)); returns final state word 7.
-__device__ __forceinline__ uint32_t scrypt_pbkdf_out(const otedama::ScryptParams& p, uint32_t nonce,
-                                                     const uint32_t X[32]) {
-  uint32_t key[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) key[i] = p.hmid[i];
-  {
-    uint32_t blk[16] = {bswap(p.hdr[16]), bswap(p.hdr[17]), bswap(p.hdr[18]), bswap(nonce), 0x80000000u,
-                        0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 640u};
-    sha256_compress(key, blk);
-  }
-  uint32_t istate[8], ostate[8];
-  hmac_states(key, istate, ostate);
-  uint32_t st[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) st[i] = istate[i];
-  uint32_t blk[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) blk[i] = bswap(X[i]);
-  sha256_compress(st, blk);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) blk[i] = bswap(X[16 + i]);
-  sha256_compress(st, blk);
-  uint32_t tail[16] = {1u, 0x80000000u, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, (64u + 132u) * 8u};
-  sha256_compress(st, tail);
-  uint32_t out[8];
-  hmac_outer(ostate, st, out);
-  return out[7];
 }
 
 // Stage 2: ROMix on X in place. `Vw` is this wave's scratch region: entry e of
@@ -615,19 +504,13 @@ static int scrypt_seg_grid(int grid) {
   return cap > 0 && cap < grid ? cap : grid;
 }
 
-// xbuf: count * 128 bytes. scratch: scrypt_scratch_bytes(grid, gap).
+// The ROMix launch(es) of one batch whose PBKDF2-in states are in X: shared by the search and the digest op.
 // gap: 1/2/4 = per-lane ROMix with that lookup gap; kScryptCoop = lane-cooperative ROMix (gap 1).
-hipError_t launch_scrypt_search(const ScryptParams& p, uint32_t base, uint32_t count, void* xbuf, void* scratch,
-                                int gap, const HitSink& sink, int grid, hipStream_t stream) {
-  uint4* X = static_cast<uint4*>(xbuf);
-  uint4* V = static_cast<uint4*>(scratch);
-  const int eg = int((count + 255) / 256);
+hipError_t launch_scrypt_romix(uint32_t count, uint4* X, uint4* V, int gap, const HitSink& sink, int grid,
+                               hipStream_t stream) {
   // The cooperative kernel runs whole waves (shfl + octet loads): round its count up to 64 lanes. xbuf is
   // allocated in multiples of 256 lanes, and lanes past `count` are ignored by pbkdf_out.
   const uint32_t count64 = (count + 63u) & ~63u;
-  // Refuse before anything is enqueued: the split ROMix holds one hash per lane slot across its two launches.
-  if (gap == kScryptCoopSplit && uint64_t(count64) > uint64_t(grid) * 256u) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(otd_scrypt_pbkdf_in, dim3(eg), dim3(256), 0, stream, p, base, count, X);
   switch (gap) {
     case kScryptCoop:  // nt lookups: +0.5-1% over default-policy loads (profiles/r1/scrypt_romix_ab.md)
       if (scrypt_segments() > 0 && uint64_t(count64) <= uint64_t(grid) * 256u) {
@@ -656,6 +539,19 @@ hipError_t launch_scrypt_search(const ScryptParams& p, uint32_t base, uint32_t c
     case 4: hipLaunchKernelGGL(otd_scrypt_romix<4>, dim3(grid), dim3(256), 0, stream, count, X, V); break;
     default: return hipErrorInvalidValue;
   }
+  return hipSuccess;
+}
+
+// xbuf: count * 128 bytes. scratch: scrypt_scratch_bytes(grid, gap).
+hipError_t launch_scrypt_search(const ScryptParams& p, uint32_t base, uint32_t count, void* xbuf, void* scratch,
+                                int gap, const HitSink& sink, int grid, hipStream_t stream) {
+  uint4* X = static_cast<uint4*>(xbuf);
+  uint4* V = static_cast<uint4*>(scratch);
+  const int eg = int((count + 255) / 256);
+  // Refuse before anything is enqueued: the split ROMix holds one hash per lane slot across its two launches.
+  if (gap == kScryptCoopSplit && uint64_t((count + 63u) & ~63u) > uint64_t(grid) * 256u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(otd_scrypt_pbkdf_in, dim3(eg), dim3(256), 0, stream, p, base, count, X);
+  if (launch_scrypt_romix(count, X, V, gap, sink, grid, stream) != hipSuccess) return hipErrorInvalidValue;
   hipLaunchKernelGGL(otd_scrypt_pbkdf_out, dim3(eg), dim3(256), 0, stream, p, base, count, X, sink);
   return hipGetLastError();
 }

@@ -3,6 +3,7 @@
 // blocks of the fixed-length inputs are folded into compile-time constants.
 // Bit-exact oracle: csrc/cpu/x11_cpu.cpp (tests/test_x11_gpu.py compares every stage).
 #include "x11_common.h"
+#include "otedama/x11_launch.h"
 
 namespace otedama {
 namespace x11k {
@@ -717,7 +718,39 @@ __global__ __launch_bounds__(kBlock) void k_blake512_80(X11Params p, u32 base, u
   blake512_80(p, base + i, h);
   store_hash(H, stride, i, h);
 }
+
+// Stage 0 of the digest op: header i at headers[5 * i] (80 bytes, 16-byte aligned), one unrelated header per lane.
+// The lane forms the job block x11_prepare hands the search (nine big-endian message words, nbits in the high half
+// of word 9) and its own nonce word from the 80 bytes, then runs the search's BLAKE-512.
+__global__ __launch_bounds__(kBlock) void k_blake512_hdr(const uint4* __restrict__ headers, u64* __restrict__ H,
+                                                        u32 stride, u32 n) {
+  const u32 i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  u32 w[20];
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    const uint4 v = headers[(size_t)i * 5 + q];
+    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+  }
+  X11Params p;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) p.m[k] = mk64(bswap32(w[2 * k + 1]), bswap32(w[2 * k]));
+  p.m9_hi = mk64(0u, bswap32(w[18]));
+  p.target_hi = 0;
+  u64 h[8];
+  blake512_80(p, w[19], h);
+  store_hash(H, stride, i, h);
+}
 }  // namespace x11k
+
+hipError_t x11_launch_blake_hdr(const uint8_t* headers, uint64_t* H, uint32_t stride, uint32_t n, hipStream_t s) {
+  using namespace x11k;
+  if (!headers || !H || n == 0 || stride < n || (reinterpret_cast<uintptr_t>(headers) & 15u))
+    return hipErrorInvalidValue;
+  k_blake512_hdr<<<dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s>>>(reinterpret_cast<const uint4*>(headers), H,
+                                                                         stride, n);
+  return hipGetLastError();
+}
 
 hipError_t x11_launch_stage_a(int stage, const X11Params& p, uint32_t base, uint64_t* H, uint32_t stride, uint32_t n,
                               X11Abort ab, hipStream_t s) {

@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "kernels/scrypt_search.hip",
     "kernels/x11_stages_a.hip",
     "kernels/x11_stages_b.hip",
+    "kernels/digest_batch.hip",
     "runtime/gpu_miner.hip",
 ]
 CXX_SOURCES = [

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import hashlib
 from dataclasses import dataclass
-from typing import Callable
+from typing import Callable, Sequence
 
 from otedama_amd.models.header import DIFF1_TARGET_INT, sha256d
 
@@ -85,3 +85,26 @@ def get(name: str) -> PowAlgorithm:
         return ALGORITHMS[name.lower()]
     except KeyError:
         raise ValueError(f"unknown algorithm {name!r}; known: {', '.join(ALGORITHMS)}") from None
+
+
+_digest_ops: dict[tuple[str, str], object] = {}  # (algorithm, device) -> ops.digest.HeaderDigest
+
+
+def hash_many(name: str, headers: Sequence[bytes], device=None) -> list[bytes]:
+    """The 32-byte LE hashes of many unrelated 80-byte headers. ``device=None``: the CPU oracle, one header at a
+    time (torch-free: usable by the engine and the pool). With a device (``"cuda:0"``): one batch through a cached
+    gfx950 digest op (``ops.digest.HeaderDigest``)."""
+    algo = get(name)
+    headers = [bytes(h) for h in headers]
+    for h in headers:
+        if len(h) != 80:
+            raise ValueError(f"header must be 80 bytes, got {len(h)}")
+    if device is None:
+        return [algo.hash(h) for h in headers]
+    from otedama_amd.ops.digest import HeaderDigest  # imports torch
+
+    key = (algo.name, str(device))
+    op = _digest_ops.get(key)
+    if op is None:
+        op = _digest_ops[key] = HeaderDigest(algo.name, device)
+    return op.hash(headers)
