@@ -65,17 +65,32 @@ def test_sha256d_matches_cpu_easy_target(seed):
 
 def test_sha256d_target_hi_tie_filtered_by_host():
     """Kernel compares only the top word; a target whose top word ties must still
-    produce only hits that the full compare accepts (host re-verification)."""
+    produce only hits that the full compare accepts (host re-verification).
+
+    The window holds a real tie: the target's top word is the top word of the digest of `star`, the nonce whose
+    top word is the median of 4096 CPU-computed digests. With the digest of `star` itself as the target the full
+    compare accepts `star`; with the same top word over tiny low bits it rejects `star`, which the kernel still
+    reports. Either way the kernel's candidates are exactly the nonces whose top word is <= the target's."""
     from otedama_amd.models.header import int_to_hash
     from otedama_amd.ops.search import Sha256dSearch
 
-    hdr = os.urandom(76) + bytes(4)
-    target_int = (0x00FFFFFF << 224) | 0x1  # top word 0x00ffffff, low bits tiny
+    hdr = __import__("random").Random(66).randbytes(76) + bytes(4)
+    base, count = 0x3C000000, 4096
+    full = {n: int.from_bytes(hashlib.sha256(hashlib.sha256(hdr[:76] + struct.pack("<I", n)).digest()).digest(),
+                              "little") for n in range(base, base + count)}
+    top = {n: h >> 224 for n, h in full.items()}
+    star = sorted(top, key=lambda n: (top[n], n))[count // 2]
+    want = sorted(n for n in top if top[n] <= top[star])
+    assert star in want and count // 2 < len(want) <= count // 2 + 2
     s = Sha256dSearch("cuda:0", cap=4096)
-    cands = s.search(hdr, int_to_hash(target_int), 0, 1 << 16)
     N = _native()
-    strict = N.cpu_scan_sha256d(hdr, int_to_hash(target_int), 0, 1 << 16)
-    assert set(strict) <= set(cands)
+    for target_int, star_is_share in ((full[star], True), ((top[star] << 224) | 0x1, False)):
+        cands = s.search(hdr, int_to_hash(target_int), base, count)
+        strict = N.cpu_scan_sha256d(hdr, int_to_hash(target_int), base, count)
+        assert set(strict) <= set(cands)
+        assert len(cands) == len(set(cands)) and sorted(cands) == want
+        assert (star in strict) == star_is_share
+        assert sorted(strict) == sorted(n for n in full if full[n] <= target_int)
 
 
 def test_sha256d_wraps_nonce_space():
