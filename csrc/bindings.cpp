@@ -22,6 +22,7 @@
 #include "otedama/clock_bounds.h"
 #include "otedama/launch_plan.h"
 #include "otedama/search_launch.h"
+#include "otedama/share_job.h"
 #include "otedama/work_queue.h"
 #include "otedama/x11.h"
 
@@ -520,6 +521,43 @@ PYBIND11_MODULE(_native, m) {
       throw std::invalid_argument("need headers, H, out != 0, n > 0, stride >= n");
     py_launch_x11_digest(headers, H, stride, n, out, stream);
   }, py::arg("headers"), py::arg("H"), py::arg("stride"), py::arg("n"), py::arg("out"), py::arg("stream") = 0);
+
+  // Share verification: the job block is opaque bytes (otedama/share_job.h), built once per job and uploaded.
+  m.def("share_job_prepare", [](const py::bytes& coinb1, const py::bytes& coinb2, int en_size,
+                                const py::bytes& prev_hash, uint32_t nbits, const std::vector<py::bytes>& branches) {
+    std::vector<std::string> bs(branches.begin(), branches.end());
+    const ShareJobBlock job = share_job_prepare(coinb1, coinb2, en_size, prev_hash, nbits, bs);
+    return py::bytes(reinterpret_cast<const char*>(&job), sizeof job);
+  }, py::arg("coinb1"), py::arg("coinb2"), py::arg("en_size"), py::arg("prev_hash"), py::arg("nbits"),
+     py::arg("branches"));
+  m.def("share_headers_cpu", [](const py::bytes& job_block, const py::bytes& records) {
+    std::string js = need(job_block, sizeof(ShareJobBlock), "job_block"), rs = records;
+    if (rs.size() % sizeof(ShareRec)) throw std::invalid_argument("records: expected a multiple of 32 bytes");
+    ShareJobBlock job;
+    std::memcpy(&job, js.data(), sizeof job);
+    std::vector<ShareRec> recs(rs.size() / sizeof(ShareRec));
+    if (!recs.empty()) std::memcpy(recs.data(), rs.data(), rs.size());
+    std::string out(recs.size() * 80, '\0');
+    share_headers_cpu(job, recs.data(), recs.size(), reinterpret_cast<uint8_t*>(&out[0]));
+    return py::bytes(out);
+  }, py::arg("job_block"), py::arg("records"));
+  m.attr("SHARE_JOB_BLOCK_SIZE") = sizeof(ShareJobBlock);
+  m.def("launch_share_headers", [](uintptr_t job, uintptr_t records, uint32_t n, uintptr_t headers,
+                                   uintptr_t stream) {
+    if (job == 0 || records == 0 || headers == 0 || n == 0)
+      throw std::invalid_argument("need job, records, headers != 0, n > 0");
+    if ((job | records | headers) & 15u) throw std::invalid_argument("job, records and headers must be 16-byte aligned");
+    py_launch_share_headers(job, records, n, headers, stream);
+  }, py::arg("job"), py::arg("records"), py::arg("n"), py::arg("headers"), py::arg("stream") = 0);
+  m.def("launch_share_verdict", [](uintptr_t job, uintptr_t records, uintptr_t digests, uintptr_t targets,
+                                   uint32_t n_targets, uint32_t n, uintptr_t verdicts, uintptr_t stream) {
+    if (job == 0 || records == 0 || digests == 0 || targets == 0 || verdicts == 0 || n == 0 || n_targets == 0)
+      throw std::invalid_argument("need job, records, digests, targets, verdicts != 0, n > 0, n_targets > 0");
+    if ((job | records | digests | targets) & 15u)
+      throw std::invalid_argument("job, records, digests and targets must be 16-byte aligned");
+    py_launch_share_verdict(job, records, digests, targets, n_targets, n, verdicts, stream);
+  }, py::arg("job"), py::arg("records"), py::arg("digests"), py::arg("targets"), py::arg("n_targets"), py::arg("n"),
+     py::arg("verdicts"), py::arg("stream") = 0);
 
   py::class_<MinerBase, std::shared_ptr<MinerBase>>(m, "Miner")
       .def("start", &MinerBase::start, py::call_guard<py::gil_scoped_release>())

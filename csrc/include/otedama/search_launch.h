@@ -43,6 +43,13 @@ void py_launch_scrypt_digest(uintptr_t headers, uint32_t n, uintptr_t xbuf, uint
 void py_launch_x11_digest(uintptr_t headers, uintptr_t H, uint32_t stride, uint32_t n, uintptr_t out,
                           uintptr_t stream);
 
+// Share verification (share_verify.hip; layouts in otedama/share_job.h): n 32-byte share records against one
+// uploaded job block -> n 80-byte headers, and n digests against a table of n_targets 32-byte targets -> n verdict
+// bytes. Same conventions as above; every array but the verdicts must be 16-byte aligned.
+void py_launch_share_headers(uintptr_t job, uintptr_t records, uint32_t n, uintptr_t headers, uintptr_t stream);
+void py_launch_share_verdict(uintptr_t job, uintptr_t records, uintptr_t digests, uintptr_t targets,
+                             uint32_t n_targets, uint32_t n, uintptr_t verdicts, uintptr_t stream);
+
 }  // namespace otedama
 
 #ifdef __HIPCC__
@@ -75,6 +82,14 @@ hipError_t launch_scrypt_digest(const uint8_t* headers, uint32_t n, void* xbuf, 
 // H: 8 * stride u64, the stage planes of the X11 chain (otedama/x11_launch.h).
 hipError_t launch_x11_digest(const uint8_t* headers, uint64_t* H, uint32_t stride, uint32_t n, uint8_t* out,
                              hipStream_t s);                              // n <= stride
+
+// Share verification. Each returns hipErrorInvalidValue, before launching anything, for n == 0, an empty target
+// table, a null pointer or an array (the job block included, the verdicts excepted) that is not 16-byte aligned.
+// job: a device copy of a ShareJobBlock.
+hipError_t launch_share_headers(const void* job, const uint8_t* records, uint32_t n, uint8_t* headers, hipStream_t s);
+hipError_t launch_share_verdict(const void* job, const uint8_t* records, const uint8_t* digests,
+                                const uint8_t* targets, uint32_t n_targets, uint32_t n, uint8_t* verdicts,
+                                hipStream_t s);
 
 }  // namespace otedama
 #endif

@@ -1,0 +1,238 @@
+// share_verify — the front and the back of "verify these pool shares" on gfx950 (layouts: otedama/share_job.h).
+//
+//   otd_share_headers  share records -> 80-byte headers. One share per lane, blocks of 256, a guard for the tail.
+//                      Per lane: the coinbase SHA-256d from the job's midstate (the tail blocks with the lane's
+//                      extranonce patched in), the merkle fold over the job's branches, the header packed as five
+//                      16-byte stores at headers + 80 * i, the layout the digest ops read (digest_batch.hip).
+//   otd_share_verdict  digests -> one verdict byte per share: the 256-bit little-endian compare (byte 31 most
+//                      significant, le256_leq of otedama/sha256.h) against the share's target and the job's network
+//                      target.
+//
+// Everything that comes from the job block is the same for every lane: the template words, the branches, the
+// midstate and the counts are read through indices formed from kernel arguments and loop counters only, so they are
+// scalar loads into SGPRs. The loops over tail blocks and branches stay rolled (their trip counts are job values);
+// the 64 rounds inside them unroll, so no array is indexed with a run-time value and nothing goes to scratch.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+
+#include "cdna_bitops.h"
+#include "otedama/search_launch.h"
+#include "otedama/share_job.h"
+
+namespace {
+using namespace otedama_dev;
+using otedama::ShareJobBlock;
+
+// The second block of every 64-byte message (cur | branch) is the padding block {0x80000000, 0 x 14, 512}: its
+// schedule and K + W are compile-time constants, so only the round function remains.
+struct PadKW {
+  uint32_t kw[64];
+};
+__device__ constexpr uint32_t c_ror(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
+__device__ constexpr PadKW pad64_kw() {
+  uint32_t w[64] = {};
+  w[0] = 0x80000000u;
+  w[15] = 512u;
+  for (int t = 16; t < 64; ++t) {
+    const uint32_t a = w[t - 15], b = w[t - 2];
+    w[t] = (c_ror(b, 17) ^ c_ror(b, 19) ^ (b >> 10)) + w[t - 7] + (c_ror(a, 7) ^ c_ror(a, 18) ^ (a >> 3)) + w[t - 16];
+  }
+  PadKW r = {};
+  for (int t = 0; t < 64; ++t) r.kw[t] = sha256_k(t) + w[t];
+  return r;
+}
+
+__device__ __forceinline__ void sha256_compress_pad64(uint32_t st[8]) {
+  constexpr PadKW kPad64 = pad64_kw();
+  uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
+#pragma unroll
+  for (int t = 0; t < 64; ++t) {
+    const uint32_t t1 = h + bS1(e) + ch(e, f, g) + kPad64.kw[t];
+    const uint32_t t2 = bS0(a) + maj(a, b, c);
+    h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+  }
+  st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h;
+}
+
+// SHA-256 of the 32-byte digest whose big-endian words are in[8]: one padded block.
+__device__ __forceinline__ void sha256_of_digest(const uint32_t in[8], uint32_t out[8]) {
+  const uint32_t blk[16] = {in[0], in[1], in[2], in[3], in[4], in[5], in[6], in[7], 0x80000000u, 0, 0, 0, 0, 0, 0, 256u};
+#pragma unroll
+  for (int k = 0; k < 8; ++k) out[k] = kSha256IVd[k];
+  sha256_compress(out, blk);
+}
+
+__device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
+
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(256) void otd_share_headers(const ShareJobBlock* __restrict__ job,
+                                                                    const uint4* __restrict__ recs, uint32_t n,
+                                                                    uint4* __restrict__ headers) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint4 r0 = recs[2 * uint64_t(i)], r1 = recs[2 * uint64_t(i) + 1];
+
+  // Job-uniform values. The counts are clamped to the block's capacity: a block that share_job_prepare did not
+  // build must still never be read past its end.
+  const uint32_t en_size = job->en_size;
+  const uint32_t en_offset = job->en_offset & 63u;
+  const uint32_t tail_blocks = umin(job->tail_blocks, uint32_t(otedama::kShareMaxTailBlocks));
+  const uint32_t n_branches = umin(job->n_branches, uint32_t(otedama::kShareMaxBranches));
+
+  // The lane's extranonce as a big-endian word stream, bytes from en_size on cleared, shifted right by the byte
+  // offset of the extranonce inside its first word: P[k] belongs to tail word (en_offset / 4) + k.
+  const uint32_t le[4] = {r0.x, r0.y, r0.z, r0.w};
+  uint32_t E[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t have = en_size > uint32_t(4 * k) ? en_size - uint32_t(4 * k) : 0u;  // bytes of this word in use
+    const uint32_t mask = have >= 4u ? 0xFFFFFFFFu : have == 3u ? 0xFFFFFF00u : have == 2u ? 0xFFFF0000u
+                        : have == 1u ? 0xFF000000u : 0u;
+    E[k] = __builtin_bswap32(le[k]) & mask;
+  }
+  const uint32_t sh = 8u * (en_offset & 3u);
+  uint32_t P[5];
+  P[0] = E[0] >> sh;
+#pragma unroll
+  for (int k = 1; k < 4; ++k) P[k] = __builtin_amdgcn_alignbit(E[k - 1], E[k], sh);
+  P[4] = __builtin_amdgcn_alignbit(E[3], 0u, sh);
+  const uint32_t w0 = en_offset >> 2;  // first tail word the extranonce touches
+
+  // coinbase txid
+  uint32_t st[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) st[k] = job->midstate[k];
+  for (uint32_t b = 0; b < tail_blocks; ++b) {
+    uint32_t msg[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) msg[j] = job->tail[16u * b + uint32_t(j)];
+    // The template holds zeros where the extranonce goes. Which of the 16 words take which P[k] is a job value, the
+    // same in every lane: selected with unrolled uniform compares, never by indexing msg or P at run time.
+    if (16u * b + 15u >= w0 && 16u * b <= w0 + 4u) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const uint32_t d = 16u * b + uint32_t(j) - w0;  // wraps to a large value below w0
+        uint32_t add = 0;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) add = d == uint32_t(k) ? P[k] : add;
+        msg[j] |= add;
+      }
+    }
+    sha256_compress(st, msg);
+  }
+  uint32_t cur[8];
+  sha256_of_digest(st, cur);
+
+  // merkle fold: cur = sha256d(cur | branch)
+  for (uint32_t b = 0; b < n_branches; ++b) {
+    uint32_t msg[16];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      msg[k] = cur[k];
+      msg[8 + k] = job->branches[8u * b + uint32_t(k)];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) st[k] = kSha256IVd[k];
+    sha256_compress(st, msg);
+    sha256_compress_pad64(st);
+    sha256_of_digest(st, cur);
+  }
+
+  // version | prev_hash | root | ntime | nbits | nonce, as little-endian words; the root's bytes are the state
+  // words big-endian
+  uint32_t root[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) root[k] = __builtin_bswap32(cur[k]);
+  uint4* h = headers + uint64_t(i) * 5u;
+  h[0] = make_uint4(r1.z, job->prev_hash[0], job->prev_hash[1], job->prev_hash[2]);
+  h[1] = make_uint4(job->prev_hash[3], job->prev_hash[4], job->prev_hash[5], job->prev_hash[6]);
+  h[2] = make_uint4(job->prev_hash[7], root[0], root[1], root[2]);
+  h[3] = make_uint4(root[3], root[4], root[5], root[6]);
+  h[4] = make_uint4(root[7], r1.x, job->nbits, r1.y);
+}
+
+namespace {
+// a <= b for 256-bit values as little-endian words, word 7 most significant: the highest differing word decides.
+__device__ __forceinline__ bool leq256(const uint32_t a[8], const uint32_t b[8]) {
+  bool r = true;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) r = a[w] != b[w] ? a[w] < b[w] : r;
+  return r;
+}
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(256) void otd_share_verdict(const ShareJobBlock* __restrict__ job,
+                                                                    const uint4* __restrict__ recs,
+                                                                    const uint4* __restrict__ digests,
+                                                                    const uint4* __restrict__ targets,
+                                                                    uint32_t n_targets, uint32_t n,
+                                                                    uint8_t* __restrict__ verdicts) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t idx = recs[2 * uint64_t(i) + 1].w;
+  if (idx >= n_targets) {  // the guard: no read of the table for an index outside it
+    verdicts[i] = otedama::kVerdictBadIndex;
+    return;
+  }
+  const uint4 d0 = digests[2 * uint64_t(i)], d1 = digests[2 * uint64_t(i) + 1];
+  const uint4 t0 = targets[2 * uint64_t(idx)], t1 = targets[2 * uint64_t(idx) + 1];
+  const uint32_t d[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+  const uint32_t t[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+  uint32_t net[8];
+#pragma unroll
+  for (int w = 0; w < 8; ++w) net[w] = job->net_target[w];
+  verdicts[i] = uint8_t((leq256(d, t) ? otedama::kVerdictShare : 0) | (leq256(d, net) ? otedama::kVerdictNetwork : 0));
+}
+
+namespace otedama {
+
+static bool aligned16(uintptr_t a) { return (a & 15u) == 0; }
+
+hipError_t launch_share_headers(const void* job, const uint8_t* records, uint32_t n, uint8_t* headers, hipStream_t s) {
+  if (n == 0 || !job || !records || !headers) return hipErrorInvalidValue;
+  if (!aligned16(reinterpret_cast<uintptr_t>(job) | reinterpret_cast<uintptr_t>(records) |
+                 reinterpret_cast<uintptr_t>(headers)))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(otd_share_headers, dim3((n + 255u) / 256u), dim3(256), 0, s,
+                     static_cast<const ShareJobBlock*>(job), reinterpret_cast<const uint4*>(records), n,
+                     reinterpret_cast<uint4*>(headers));
+  return hipGetLastError();
+}
+
+hipError_t launch_share_verdict(const void* job, const uint8_t* records, const uint8_t* digests, const uint8_t* targets,
+                                uint32_t n_targets, uint32_t n, uint8_t* verdicts, hipStream_t s) {
+  if (n == 0 || n_targets == 0 || !job || !records || !digests || !targets || !verdicts) return hipErrorInvalidValue;
+  if (!aligned16(reinterpret_cast<uintptr_t>(job) | reinterpret_cast<uintptr_t>(records) |
+                 reinterpret_cast<uintptr_t>(digests) | reinterpret_cast<uintptr_t>(targets)))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(otd_share_verdict, dim3((n + 255u) / 256u), dim3(256), 0, s,
+                     static_cast<const ShareJobBlock*>(job), reinterpret_cast<const uint4*>(records),
+                     reinterpret_cast<const uint4*>(digests), reinterpret_cast<const uint4*>(targets), n_targets, n,
+                     verdicts);
+  return hipGetLastError();
+}
+
+static void check(hipError_t e, const char* what) {
+  if (e != hipSuccess) throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(e) + " at " + what);
+}
+
+void py_launch_share_headers(uintptr_t job, uintptr_t records, uint32_t n, uintptr_t headers, uintptr_t stream) {
+  check(launch_share_headers(reinterpret_cast<const void*>(job), reinterpret_cast<const uint8_t*>(records), n,
+                             reinterpret_cast<uint8_t*>(headers), reinterpret_cast<hipStream_t>(stream)),
+        "launch_share_headers");
+}
+
+void py_launch_share_verdict(uintptr_t job, uintptr_t records, uintptr_t digests, uintptr_t targets,
+                             uint32_t n_targets, uint32_t n, uintptr_t verdicts, uintptr_t stream) {
+  check(launch_share_verdict(reinterpret_cast<const void*>(job), reinterpret_cast<const uint8_t*>(records),
+                             reinterpret_cast<const uint8_t*>(digests), reinterpret_cast<const uint8_t*>(targets),
+                             n_targets, n, reinterpret_cast<uint8_t*>(verdicts),
+                             reinterpret_cast<hipStream_t>(stream)),
+        "launch_share_verdict");
+}
+
+}  // namespace otedama

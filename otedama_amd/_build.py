@@ -30,6 +30,7 @@ HIP_SOURCES = [
     "kernels/x11_stages_a.hip",
     "kernels/x11_stages_b.hip",
     "kernels/digest_batch.hip",
+    "kernels/share_verify.hip",
     "runtime/gpu_miner.hip",
 ]
 CXX_SOURCES = [
@@ -38,6 +39,7 @@ CXX_SOURCES = [
     "cpu/aead.cpp",
     "cpu/x11_cpu.cpp",
     "cpu/sv2_frame.cpp",
+    "cpu/share_job.cpp",
     "runtime/miner_common.cpp",
     "bindings.cpp",
 ]

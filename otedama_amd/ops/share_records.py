@@ -1,0 +1,52 @@
+"""The 32-byte share record of the share-verification op (csrc/include/otedama/share_job.h ``ShareRec``), packed
+and unpacked without torch, so the pool layer (pool/batch.py) can form a batch before it decides whether a GPU is
+involved at all. ``ops.verify`` re-exports these.
+
+    bytes 0..15   extranonce (the first ``en_size`` bytes are used, the rest are zero)
+    bytes 16..19  ntime      bytes 20..23  nonce      bytes 24..27  version (full rolled version)
+    bytes 28..31  index into the target table of the launch          (all little-endian)
+"""
+from __future__ import annotations
+
+import struct
+from typing import Sequence
+
+RECORD_BYTES = 32
+MAX_EXTRANONCE = 16
+VERDICT_SHARE = 1       # hash <= targets[index]
+VERDICT_NETWORK = 2     # hash <= the network target of the job's nbits
+VERDICT_BAD_INDEX = 0x80  # index outside the target table; no other bit is set
+
+_REC = struct.Struct("<16sIIII")
+
+
+def pack_records(shares: Sequence[tuple], target_indices: Sequence[int], en_size: int) -> bytes:
+    """``shares``: ``(extranonce, ntime, nonce, version)`` tuples, every extranonce exactly ``en_size`` bytes (a
+    longer or shorter one is a different coinbase and raises ``ValueError``). Integers are taken modulo 2^32, as
+    ``PoolServer.header_for`` packs them."""
+    if not 1 <= en_size <= MAX_EXTRANONCE:
+        raise ValueError(f"en_size must be in 1..{MAX_EXTRANONCE}")
+    if len(shares) != len(target_indices):
+        raise ValueError("one target index per share")
+    out = bytearray(RECORD_BYTES * len(shares))
+    for i, ((en, ntime, nonce, version), idx) in enumerate(zip(shares, target_indices)):
+        en = bytes(en)
+        if len(en) != en_size:
+            raise ValueError(f"extranonce of share {i} is {len(en)} bytes, the job takes {en_size}")
+        if not 0 <= idx < 1 << 32:
+            raise ValueError(f"target index of share {i} does not fit 32 bits")
+        _REC.pack_into(out, RECORD_BYTES * i, en, ntime & 0xFFFFFFFF, nonce & 0xFFFFFFFF, version & 0xFFFFFFFF, idx)
+    return bytes(out)
+
+
+def unpack_records(records: bytes, en_size: int) -> tuple[list[tuple], list[int]]:
+    """Inverse of :func:`pack_records`: ``(shares, target_indices)``."""
+    if not 1 <= en_size <= MAX_EXTRANONCE:
+        raise ValueError(f"en_size must be in 1..{MAX_EXTRANONCE}")
+    if len(records) % RECORD_BYTES:
+        raise ValueError(f"records must be a multiple of {RECORD_BYTES} bytes")
+    shares, indices = [], []
+    for en, ntime, nonce, version, idx in _REC.iter_unpack(records):
+        shares.append((en[:en_size], ntime, nonce, version))
+        indices.append(idx)
+    return shares, indices

@@ -1,0 +1,137 @@
+"""Share verification op: a batch of pool shares in, verdicts out, in one enqueue.
+
+A pool never holds the 80-byte headers it has to hash. It holds a job (coinb1, coinb2, merkle branches, prev_hash,
+nbits) and receives shares ``(extranonce, ntime, nonce, version)``. :class:`ShareVerify` puts a front and a back on
+the digest ops (:mod:`otedama_amd.ops.digest`):
+
+  1. ``otd_share_headers``  share records -> headers: the coinbase SHA-256d from the job's midstate and the merkle
+     fold, one share per lane (csrc/kernels/share_verify.hip)
+  2. the ``HeaderDigest`` launches of the op's algorithm
+  3. ``otd_share_verdict``  the 256-bit little-endian compare against per-share targets and the network target
+
+Layouts of the job block and the share record: csrc/include/otedama/share_job.h. The record packer is torch-free
+(:mod:`otedama_amd.ops.share_records`) and re-exported here.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Sequence
+
+import torch
+
+from otedama_amd.ops.digest import ALIGN, DIGEST_BYTES, HEADER_BYTES, HeaderDigest
+from otedama_amd.ops.share_records import (MAX_EXTRANONCE, RECORD_BYTES, VERDICT_BAD_INDEX, VERDICT_NETWORK,  # noqa: F401
+                                           VERDICT_SHARE, pack_records, unpack_records)
+
+TARGET_BYTES = 32
+
+
+@dataclass
+class PreparedJob:
+    block: bytes          # ShareJobBlock (opaque)
+    dev: torch.Tensor     # uint8 device copy of the block
+    en_size: int
+
+
+class ShareVerify:
+    """Reusable share verifier for one algorithm on one device. It owns a :class:`HeaderDigest` of the same
+    algorithm and the headers buffer between the two; ``capacity`` and ``grid`` are the digest op's."""
+
+    def __init__(self, algorithm: str, device="cuda:0", capacity: int | None = None, grid: int | None = None):
+        self.digest = HeaderDigest(algorithm, device, capacity=capacity, grid=grid)
+        self.algorithm = self.digest.algorithm
+        self.native = self.digest.native
+        self.device = self.digest.device
+        self.headers: torch.Tensor | None = None  # uint8 [rows, 80], grown to the largest batch seen
+        self._last_stream = None
+
+    def prepare(self, coinb1: bytes, coinb2: bytes, en_size: int, prev_hash: bytes, nbits: int,
+                branches: Sequence[bytes]) -> PreparedJob:
+        """Build the job block (midstate, padded tail template, branches, network target) and upload it. A job over
+        the block's limits (tail of more than 32 blocks, more than 32 branches, ``en_size`` outside 1..16) raises
+        ``ValueError``: verify it on the CPU."""
+        block = self.native.share_job_prepare(bytes(coinb1), bytes(coinb2), int(en_size), bytes(prev_hash),
+                                              int(nbits) & 0xFFFFFFFF, [bytes(b) for b in branches])
+        dev = torch.frombuffer(bytearray(block), dtype=torch.uint8).to(self.device)
+        return PreparedJob(block, dev, int(en_size))
+
+    def _check(self, job: PreparedJob, records: torch.Tensor, targets: torch.Tensor) -> int:
+        if not isinstance(job, PreparedJob) or not isinstance(job.dev, torch.Tensor):
+            raise ValueError("job must come from prepare()")
+        if job.dev.device != self.device:
+            raise ValueError(f"job was prepared for {job.dev.device}, the op runs on {self.device}")
+        if (job.dev.dtype != torch.uint8 or job.dev.numel() != self.native.SHARE_JOB_BLOCK_SIZE
+                or not job.dev.is_contiguous() or job.dev.data_ptr() % ALIGN):
+            raise ValueError("job block has the wrong size or alignment")
+        for name, t, width in (("records", records, RECORD_BYTES), ("targets", targets, TARGET_BYTES)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+                raise ValueError(f"{name} must be a uint8 tensor")
+            if t.dim() != 2 or t.shape[1] != width:
+                raise ValueError(f"{name} must have shape [n, {width}]")
+            if t.device != self.device:
+                raise ValueError(f"{name} must live on {self.device}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            if t.shape[0] and t.data_ptr() % ALIGN:
+                raise ValueError(f"{name} must start at a {ALIGN}-byte aligned address")
+        if targets.shape[0] < 1:
+            raise ValueError("the target table is empty")
+        if records.shape[0] >= 1 << 32 or targets.shape[0] >= 1 << 32:
+            raise ValueError("at most 2^32 - 1 records and targets per launch")
+        return records.shape[0]
+
+    def launch(self, job: PreparedJob, records: torch.Tensor, targets: torch.Tensor,
+               stream: torch.cuda.Stream | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Enqueue headers, digests and verdicts of ``records`` (uint8 ``[n, 32]``) against ``targets`` (uint8
+        ``[t, 32]``, ``t >= 1``; both contiguous, 16-byte aligned, on the op's device) on ``stream`` (default: the
+        current stream, which the given stream first waits for) and return ``(verdicts uint8 [n], digests uint8
+        [n, 32], headers uint8 [n, 80])`` without synchronising. ``headers`` is a view of the op's own buffer and is
+        overwritten by the next launch. A bad argument raises ``ValueError`` before anything is enqueued."""
+        n = self._check(job, records, targets)
+        cur = torch.cuda.current_stream(self.device)
+        if stream is None:
+            stream = cur
+        elif stream != cur:
+            stream.wait_stream(cur)  # the caller produced `records` and `targets` on the current stream
+        with torch.cuda.stream(stream):
+            verdicts = torch.empty(n, dtype=torch.uint8, device=self.device)
+            digests = torch.empty((n, DIGEST_BYTES), dtype=torch.uint8, device=self.device)
+        if n == 0:
+            return verdicts, digests, torch.empty((0, HEADER_BYTES), dtype=torch.uint8, device=self.device)
+        if self._last_stream is not None and self._last_stream != stream:
+            stream.wait_stream(self._last_stream)  # the headers buffer is still in use by the previous launch
+        if self.headers is None or self.headers.shape[0] < n:
+            if self.headers is not None and self._last_stream is not None:
+                self.headers.record_stream(self._last_stream)
+            with torch.cuda.stream(stream):
+                self.headers = torch.empty((n, HEADER_BYTES), dtype=torch.uint8, device=self.device)
+        self._last_stream = stream
+        headers = self.headers[:n]
+        s = stream.cuda_stream
+        self.native.launch_share_headers(job.dev.data_ptr(), records.data_ptr(), n, headers.data_ptr(), s)
+        self.digest.launch(headers, out=digests, stream=stream)
+        self.native.launch_share_verdict(job.dev.data_ptr(), records.data_ptr(), digests.data_ptr(),
+                                         targets.data_ptr(), targets.shape[0], n, verdicts.data_ptr(), s)
+        return verdicts, digests, headers
+
+    def verify(self, job: PreparedJob, shares: Sequence[tuple], targets: Sequence[bytes],
+               target_indices: Sequence[int] | None = None) -> tuple[list[int], list[bytes], list[bytes]]:
+        """Synchronous convenience: ``(extranonce, ntime, nonce, version)`` tuples and 32-byte targets in, the lists
+        ``(verdict bytes, 32-byte hashes, 80-byte headers)`` out. ``target_indices`` defaults to target 0 for every
+        share."""
+        targets = [bytes(t) for t in targets]
+        if not targets or any(len(t) != TARGET_BYTES for t in targets):
+            raise ValueError(f"need at least one target, each {TARGET_BYTES} bytes")
+        if target_indices is None:
+            target_indices = [0] * len(shares)
+        packed = pack_records(shares, target_indices, job.en_size)
+        if not shares:
+            return [], [], []
+        recs = torch.frombuffer(bytearray(packed), dtype=torch.uint8).view(len(shares), RECORD_BYTES)
+        tgts = torch.frombuffer(bytearray(b"".join(targets)), dtype=torch.uint8).view(len(targets), TARGET_BYTES)
+        v, d, h = self.launch(job, recs.to(self.device), tgts.to(self.device))
+        torch.cuda.current_stream(self.device).synchronize()
+        vb, db, hb = (t.cpu().numpy().tobytes() for t in (v, d, h))
+        n = len(shares)
+        return (list(vb), [db[i * DIGEST_BYTES:(i + 1) * DIGEST_BYTES] for i in range(n)],
+                [hb[i * HEADER_BYTES:(i + 1) * HEADER_BYTES] for i in range(n)])

@@ -1,0 +1,85 @@
+"""Batch share checking for the pool: shares of one job in, ``(header, hash, verdict byte)`` out.
+
+``device=None`` is the oracle: today's Python functions, one share at a time (sha256d of the coinbase,
+``merkle_root_from_branches``, the header packed as ``PoolServer.header_for`` packs it, the algorithm's CPU hash,
+integer compares). With a device the whole batch is one ``ops.verify.ShareVerify.verify``: headers, hashes and
+compares happen on the GPU. Both paths return the same list. Importing this module imports neither torch nor the
+native extension.
+"""
+from __future__ import annotations
+
+import struct
+from dataclasses import dataclass, field
+from typing import Sequence
+
+from otedama_amd.models import algorithms
+from otedama_amd.models.header import hash_to_int, sha256d, target_from_nbits
+from otedama_amd.ops.share_records import VERDICT_BAD_INDEX, VERDICT_NETWORK, VERDICT_SHARE
+from otedama_amd.pool.template import merkle_root_from_branches
+
+
+@dataclass(frozen=True)
+class ShareJob:
+    """What every share of one job has in common. ``en_size``: bytes of extranonce between the coinbase parts."""
+    coinb1: bytes
+    coinb2: bytes
+    en_size: int
+    prev_hash: bytes
+    nbits: int
+    branches: list = field(default_factory=list)
+
+
+_verify_ops: dict[tuple[str, str], object] = {}  # (algorithm, device) -> ops.verify.ShareVerify
+
+
+def header_of(job: ShareJob, extranonce: bytes, ntime: int, nonce: int, version: int) -> bytes:
+    root = merkle_root_from_branches(sha256d(job.coinb1 + extranonce + job.coinb2), job.branches)
+    return (struct.pack("<I", version & 0xFFFFFFFF) + job.prev_hash + root
+            + struct.pack("<III", ntime & 0xFFFFFFFF, job.nbits & 0xFFFFFFFF, nonce & 0xFFFFFFFF))
+
+
+def check_shares(algorithm: str, job: ShareJob, shares: Sequence[tuple], targets: Sequence[bytes],
+                 target_indices: Sequence[int], device=None) -> list[tuple[bytes, bytes, int]]:
+    """``shares``: ``(extranonce, ntime, nonce, version)`` tuples against ``job``; share ``i`` is compared with
+    ``targets[target_indices[i]]`` (32 bytes, little-endian) and with the network target of ``job.nbits``. Returns
+    ``(header, hash, verdict)`` per share: verdict bit 0 = hash <= share target, bit 1 = hash <= network target,
+    ``0x80`` alone for an index outside the table. A job over the GPU job block's limits is checked on the CPU."""
+    algo = algorithms.get(algorithm)
+    shares = [(bytes(en), int(ntime), int(nonce), int(version)) for en, ntime, nonce, version in shares]
+    targets = [bytes(t) for t in targets]
+    if not targets or any(len(t) != 32 for t in targets):
+        raise ValueError("need at least one target, each 32 bytes")
+    if len(target_indices) != len(shares):
+        raise ValueError("one target index per share")
+    if len(job.prev_hash) != 32:
+        raise ValueError("prev_hash must be 32 bytes")
+    for i, s in enumerate(shares):
+        if len(s[0]) != job.en_size:
+            raise ValueError(f"extranonce of share {i} is {len(s[0])} bytes, the job takes {job.en_size}")
+    network = hash_to_int(target_from_nbits(job.nbits))
+    if device is not None and shares:
+        from otedama_amd.ops.verify import ShareVerify  # imports torch
+
+        key = (algo.name, str(device))
+        op = _verify_ops.get(key)
+        if op is None:
+            op = _verify_ops[key] = ShareVerify(algo.name, device)
+        try:
+            prepared = op.prepare(job.coinb1, job.coinb2, job.en_size, job.prev_hash, job.nbits, job.branches)
+        except ValueError:
+            prepared = None  # over the block's limits: the oracle path below
+        if prepared is not None:
+            verdicts, hashes, headers = op.verify(prepared, shares, targets, target_indices)
+            return list(zip(headers, hashes, verdicts))
+    out = []
+    tints = [hash_to_int(t) for t in targets]
+    for (en, ntime, nonce, version), idx in zip(shares, target_indices):
+        hdr = header_of(job, en, ntime, nonce, version)
+        h = algo.hash(hdr)
+        if not 0 <= idx < len(tints):
+            verdict = VERDICT_BAD_INDEX
+        else:
+            hv = hash_to_int(h)
+            verdict = (VERDICT_SHARE if hv <= tints[idx] else 0) | (VERDICT_NETWORK if hv <= network else 0)
+        out.append((hdr, h, verdict))
+    return out

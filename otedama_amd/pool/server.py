@@ -365,6 +365,48 @@ class PoolServer:
         self._validate_log.append((time.monotonic(), ms))
         return v
 
+    def validate_many(self, items: list, device=None) -> list[Verdict]:
+        """validate() over a batch: ``items`` are ``(worker, job_id, extranonce, ntime, nonce, version)``. The
+        verdicts, counters, reject reasons and journal rows are those of validate() on the items in order (in-batch
+        duplicates and a block found mid-batch included); the headers and hashes of the shares that pass the field
+        checks are computed per distinct job in one ``pool.batch.check_shares`` call: on the CPU (``device=None``) or
+        as one GPU batch (``device="cuda:0"``). The difficulty, grace and block logic stays in _finish, on the
+        returned hashes."""
+        from otedama_amd.pool.batch import ShareJob, check_shares
+
+        # 1. field checks in order; nothing is counted or journalled yet, so the rows keep the order of the items
+        checked = [self._field_check(w, job_id, ntime, version) for w, job_id, _en, ntime, _nonce, version in items]
+        # 2. headers and hashes of the survivors, one call per distinct job (and extranonce length)
+        groups: dict[tuple[int, int], list[int]] = {}
+        for i, (job, item) in enumerate(zip(checked, items)):
+            if not isinstance(job, str):
+                groups.setdefault((job.job_int, len(item[2])), []).append(i)
+        hashed: dict[int, tuple[bytes, bytes]] = {}
+        for (_job_int, en_size), idxs in groups.items():
+            job = checked[idxs[0]]
+            sj = ShareJob(job.coinb1, job.coinb2, en_size, job.block.prev_hash, job.block.nbits, job.branches)
+            table: dict[bytes, int] = {}
+            tidx = [table.setdefault(self.share_target(items[i][0].vd.difficulty), len(table)) for i in idxs]
+            shares = [(items[i][2], items[i][3], items[i][4], items[i][5]) for i in idxs]
+            if 1 <= en_size <= 16:
+                res = check_shares(self.algo.name, sj, shares, list(table), tidx, device)
+                for i, (hdr, h, _bits) in zip(idxs, res):
+                    hashed[i] = (hdr, h)
+            else:  # no such extranonce in the job block's record: one at a time, as validate() does
+                for i, (en, ntime, nonce, version) in zip(idxs, shares):
+                    hdr = self.header_for(job, en, version, ntime, nonce)
+                    hashed[i] = (hdr, self.algo.hash(hdr))
+        # 3. verdicts in order: _finish repeats the stale and duplicate checks of _precheck
+        out = []
+        for i, (job, item) in enumerate(zip(checked, items)):
+            worker, job_id = item[0], item[1]
+            if isinstance(job, str):
+                out.append(self._reject(worker, job_id, job))
+            else:
+                hdr, h = hashed[i]
+                out.append(self._finish(worker, job_id, job, hdr, h))
+        return out
+
     def share_target(self, difficulty: float) -> bytes:
         """Share target for a difficulty, clamped to 2^256-1 (below ~diff1/2^256 the target would overflow)."""
         try:
@@ -372,14 +414,21 @@ class PoolServer:
         except TargetError:
             return b"\xff" * 32
 
-    def _precheck(self, worker: _Worker, job_id: str, extranonce: bytes, ntime: int, nonce: int, version: int):
+    def _field_check(self, worker: _Worker, job_id: str, ntime: int, version: int) -> "PoolJob | str":
+        """Checks 1..3 of a submitted share, without side effects: the job, or the reject reason."""
         job = self.jobs.get(job_id)
         if job is None or job.block is not self.block:
-            return self._reject(worker, job_id, "stale-job")
+            return "stale-job"
         if (version ^ job.version) & ~worker.version_mask & 0xFFFFFFFF:
-            return self._reject(worker, job_id, "invalid-version-bits")
+            return "invalid-version-bits"
         if ntime < job.ntime or ntime > max(time.time(), job.ntime) + MAX_NTIME_FUTURE:
-            return self._reject(worker, job_id, "invalid-ntime")
+            return "invalid-ntime"
+        return job
+
+    def _precheck(self, worker: _Worker, job_id: str, extranonce: bytes, ntime: int, nonce: int, version: int):
+        job = self._field_check(worker, job_id, ntime, version)
+        if isinstance(job, str):
+            return self._reject(worker, job_id, job)
         # Duplicates are keyed on the full 80-byte header, not on the job id: every job of one block shares the
         # coinbase parts and merkle branches, so one (extranonce, ntime, nonce, version) submitted under several
         # live job ids is the same work and is credited once.

@@ -29,6 +29,14 @@ for name in tsan asan; do
   fi
   [ "$rc" -eq 0 ] || { echo "$name run failed (rc=$rc)"; exit "$rc"; }
 done
+# The share job block (csrc/cpu/share_job.cpp) under ASan + UBSan: builder and walker over the length grid of the CPU
+# tests, and the limit violations. A stand-alone program, host code only.
+sj="$OUT/share_job_check"
+# shellcheck disable=SC2086
+"$CXX" "${FLAGS[@]}" ${SAN[asan]} "$ROOT/csrc/cpu/sha256_cpu.cpp" "$ROOT/csrc/cpu/share_job.cpp" \
+  "$ROOT/tools/sanitize/share_job_check.cpp" -o "$sj" -lcrypto
+echo "== share job block: $sj"
+ASAN_OPTIONS="detect_leaks=1 abort_on_error=0" UBSAN_OPTIONS="print_stacktrace=1" "$sj" || { echo "share_job_check failed"; exit 1; }
 # libFuzzer (ASan + UBSan) over the SV2 frame scanner and the CPU hash paths.
 fz="$OUT/fuzz_native"
 "$CXX" -std=c++17 -O1 -g -march=x86-64-v2 "-I$ROOT/csrc/include" -fsanitize=fuzzer,address,undefined \
