@@ -559,6 +559,33 @@ PYBIND11_MODULE(_native, m) {
   }, py::arg("job"), py::arg("records"), py::arg("digests"), py::arg("targets"), py::arg("n_targets"), py::arg("n"),
      py::arg("verdicts"), py::arg("stream") = 0);
 
+  // Live share verification: 128-byte result records (otedama/share_job.h ShareResult).
+  m.def("share_results_cpu", [](const py::bytes& job_block, const py::bytes& records, const py::bytes& targets) {
+    std::string js = need(job_block, sizeof(ShareJobBlock), "job_block"), rs = records, ts = targets;
+    if (rs.size() % sizeof(ShareRec)) throw std::invalid_argument("records: expected a multiple of 32 bytes");
+    if (ts.empty() || ts.size() % 32) throw std::invalid_argument("targets: expected a non-empty multiple of 32 bytes");
+    ShareJobBlock job;
+    std::memcpy(&job, js.data(), sizeof job);
+    std::vector<ShareRec> recs(rs.size() / sizeof(ShareRec));
+    if (!recs.empty()) std::memcpy(recs.data(), rs.data(), rs.size());
+    std::vector<ShareResult> out(recs.size());
+    share_results_cpu(job, recs.data(), recs.size(), reinterpret_cast<const uint8_t*>(ts.data()), ts.size() / 32,
+                      out.data());
+    return py::bytes(reinterpret_cast<const char*>(out.data()), out.size() * sizeof(ShareResult));
+  }, py::arg("job_block"), py::arg("records"), py::arg("targets"));
+  m.attr("SHARE_RESULT_BYTES") = sizeof(ShareResult);
+  m.def("launch_share_pack", [](uintptr_t job, uintptr_t records, uintptr_t headers, uintptr_t digests,
+                                uintptr_t targets, uint32_t n_targets, uint32_t n, uintptr_t results,
+                                uintptr_t stream) {
+    if (job == 0 || records == 0 || headers == 0 || digests == 0 || targets == 0 || results == 0 || n == 0 ||
+        n_targets == 0)
+      throw std::invalid_argument("need job, records, headers, digests, targets, results != 0, n > 0, n_targets > 0");
+    if ((job | records | headers | digests | targets | results) & 15u)
+      throw std::invalid_argument("job, records, headers, digests, targets and results must be 16-byte aligned");
+    py_launch_share_pack(job, records, headers, digests, targets, n_targets, n, results, stream);
+  }, py::arg("job"), py::arg("records"), py::arg("headers"), py::arg("digests"), py::arg("targets"),
+     py::arg("n_targets"), py::arg("n"), py::arg("results"), py::arg("stream") = 0);
+
   py::class_<MinerBase, std::shared_ptr<MinerBase>>(m, "Miner")
       .def("start", &MinerBase::start, py::call_guard<py::gil_scoped_release>())
       .def("stop", &MinerBase::stop, py::call_guard<py::gil_scoped_release>())

@@ -139,4 +139,23 @@ void share_headers_cpu(const ShareJobBlock& job, const ShareRec* recs, size_t n,
   }
 }
 
+void share_results_cpu(const ShareJobBlock& job, const ShareRec* recs, size_t n, const uint8_t* targets,
+                       size_t n_targets, ShareResult* out) {
+  if (n_targets == 0 || !targets) throw std::invalid_argument("the target table is empty");
+  uint8_t net[32];
+  for (int k = 0; k < 8; ++k) store_le32(net + 4 * k, job.net_target[k]);
+  for (size_t i = 0; i < n; ++i) {
+    ShareResult& r = out[i];
+    std::memset(&r, 0, sizeof r);
+    share_headers_cpu(job, recs + i, 1, r.header);
+    sha256d(r.header, 80, r.hash);
+    const uint32_t idx = recs[i].target_index;
+    if (idx >= n_targets)
+      r.verdict = kVerdictBadIndex;
+    else
+      r.verdict = uint8_t((le256_leq(r.hash, targets + 32 * size_t(idx)) ? kVerdictShare : 0) |
+                          (le256_leq(r.hash, net) ? kVerdictNetwork : 0));
+  }
+}
+
 }  // namespace otedama

@@ -50,6 +50,11 @@ void py_launch_share_headers(uintptr_t job, uintptr_t records, uint32_t n, uintp
 void py_launch_share_verdict(uintptr_t job, uintptr_t records, uintptr_t digests, uintptr_t targets,
                              uint32_t n_targets, uint32_t n, uintptr_t verdicts, uintptr_t stream);
 
+// Live share verification (share_results.hip): the headers and digests of the chain above -> n 128-byte ShareResult
+// records, with the compares done there. Every array is 16-byte aligned.
+void py_launch_share_pack(uintptr_t job, uintptr_t records, uintptr_t headers, uintptr_t digests, uintptr_t targets,
+                          uint32_t n_targets, uint32_t n, uintptr_t results, uintptr_t stream);
+
 }  // namespace otedama
 
 #ifdef __HIPCC__
@@ -90,6 +95,9 @@ hipError_t launch_share_headers(const void* job, const uint8_t* records, uint32_
 hipError_t launch_share_verdict(const void* job, const uint8_t* records, const uint8_t* digests,
                                 const uint8_t* targets, uint32_t n_targets, uint32_t n, uint8_t* verdicts,
                                 hipStream_t s);
+// The same conventions; here every array, the results included, is 16-byte aligned.
+hipError_t launch_share_pack(const void* job, const uint8_t* records, const uint8_t* headers, const uint8_t* digests,
+                             const uint8_t* targets, uint32_t n_targets, uint32_t n, uint8_t* results, hipStream_t s);
 
 }  // namespace otedama
 #endif

@@ -30,6 +30,15 @@ constexpr uint8_t kVerdictShare = 1;      // hash <= targets[target_index]
 constexpr uint8_t kVerdictNetwork = 2;    // hash <= the network target of nbits
 constexpr uint8_t kVerdictBadIndex = 0x80;  // target_index outside the table; no other bit is set
 
+// One verified share, as the live path returns it (csrc/kernels/share_results.hip): eight 16-byte stores.
+struct alignas(16) ShareResult {
+  uint8_t header[80];  // the bytes otd_share_headers writes
+  uint8_t hash[32];    // the algorithm's hash of the header
+  uint8_t verdict;     // as above; for kVerdictBadIndex the table was not read, header and hash are still written
+  uint8_t zero[15];    // written as zeros
+};
+static_assert(sizeof(ShareResult) == 128, "ShareResult is 128 bytes");
+
 // One job. Everything a kernel reads from it is the same for every share of the launch (wave-uniform).
 //   coinbase = coinb1 | extranonce | coinb2. `midstate` is the SHA-256 state after the whole 64-byte blocks that lie
 //   entirely inside coinb1; `tail` is the rest, coinb1_tail | zeros(en_size) | coinb2 with the SHA-256 padding and
@@ -62,5 +71,13 @@ ShareJobBlock share_job_prepare(const std::string& coinb1, const std::string& co
 // The job block walked in plain C++: n records -> n 80-byte headers at out + 80 * i, what otd_share_headers
 // writes. Throws std::invalid_argument for a block that share_job_prepare could not have produced.
 void share_headers_cpu(const ShareJobBlock& job, const ShareRec* recs, size_t n, uint8_t* out);
+
+// What the live path writes for SHA-256d (otd_share_headers, the digest launch, otd_share_pack), in plain C++: n
+// records against a table of n_targets 32-byte little-endian targets -> n ShareResult records (SHA-256d of
+// share_headers_cpu's header, le256_leq against the share's target and the job's network target). A target index
+// outside the table gives kVerdictBadIndex with header and hash still written. Throws std::invalid_argument like
+// share_headers_cpu, and for an empty table.
+void share_results_cpu(const ShareJobBlock& job, const ShareRec* recs, size_t n, const uint8_t* targets,
+                       size_t n_targets, ShareResult* out);
 
 }  // namespace otedama

@@ -31,6 +31,7 @@ HIP_SOURCES = [
     "kernels/x11_stages_b.hip",
     "kernels/digest_batch.hip",
     "kernels/share_verify.hip",
+    "kernels/share_results.hip",
     "runtime/gpu_miner.hip",
 ]
 CXX_SOURCES = [

@@ -36,6 +36,8 @@ def apply_config_file(fs: FlagSet, stderr: TextIO) -> None:
     pairs = (("algorithms", ps.algorithm), ("listen-sv2", ps.listen_sv2), ("listen-v1", ps.listen_v1),
              ("difficulty", ps.initial_difficulty), ("share-seconds", ps.target_share_seconds),
              ("retarget-seconds", ps.vardiff_retarget_seconds), ("journal", ps.journal_path),
+             ("verify-device", ps.verify_device), ("verify-batch-ms", ps.verify_batch_ms),
+             ("verify-batch-max", ps.verify_batch_max), ("verify-min-gpu", ps.verify_min_gpu),
              ("http-addr", cfg.http_addr))
     default = type(ps)()
     for flag, value in pairs:
@@ -48,10 +50,30 @@ def apply_config_file(fs: FlagSet, stderr: TextIO) -> None:
 
 _FILE_FIELD = {"algorithms": "algorithm", "listen-sv2": "listen_sv2", "listen-v1": "listen_v1",
                "difficulty": "initial_difficulty", "share-seconds": "target_share_seconds",
-               "retarget-seconds": "vardiff_retarget_seconds", "journal": "journal_path"}
+               "retarget-seconds": "vardiff_retarget_seconds", "journal": "journal_path",
+               "verify-device": "verify_device", "verify-batch-ms": "verify_batch_ms",
+               "verify-batch-max": "verify_batch_max", "verify-min-gpu": "verify_min_gpu"}
 
 
-def cmd_pool(args: list[str], stdout: TextIO, stderr: TextIO) -> int:
+def verify_options(fs: FlagSet) -> dict:
+    """The micro-batcher's PoolOptions fields from the (file-filled) flags."""
+    return {"verify_device": fs["verify-device"], "verify_batch_ms": fs["verify-batch-ms"],
+            "verify_batch_max": fs["verify-batch-max"], "verify_min_gpu": fs["verify-min-gpu"]}
+
+
+def verify_options_error(opts: dict) -> str | None:
+    from otedama_amd.pool.microbatch import valid_device
+
+    if not valid_device(opts["verify_device"]):
+        return f"--verify-device {opts['verify_device']!r} must be empty (off), cpu or cuda:N"
+    if opts["verify_batch_ms"] <= 0 or opts["verify_batch_max"] <= 0:
+        return "--verify-batch-ms and --verify-batch-max must be positive"
+    if opts["verify_min_gpu"] < 0:
+        return "--verify-min-gpu must not be negative (0 = the algorithm's measured default)"
+    return None
+
+
+def pool_flags(stderr: TextIO) -> FlagSet:
     fs = FlagSet("pool", stderr)
     fs.string("algorithms", "sha256d", "Comma-separated algorithms to serve (sha256d, scrypt, x11).")
     fs.string("listen-sv2", "127.0.0.1:3336", "Stratum V2 listen address (port +1 per extra algorithm).")
@@ -71,7 +93,16 @@ def cmd_pool(args: list[str], stdout: TextIO, stderr: TextIO) -> int:
     fs.string("noise-suite", "", "Noise suites accepted: empty = both, ellswift (current SV2) or legacy.")
     fs.string("noise-authority-key", "", "Hex secp256k1 secret signing the Noise certificate (empty = fresh per run).")
     fs.float("duration", 0.0, "Stop after this many seconds (0 = run until signalled).")
+    fs.string("verify-device", "", "Validate submits in micro-batches: cpu or cuda:N (empty = off, one share at a time).")
+    fs.float("verify-batch-ms", 2.0, "Micro-batch flush delay after the oldest pending submit, in milliseconds.")
+    fs.int("verify-batch-max", 4096, "Micro-batch flush size.")
+    fs.int("verify-min-gpu", 0, "Batches with fewer shares are hashed on the CPU (0 = the algorithm's measured default).")
     fs.string("config", "", "Path to the YAML config file (default: $OTEDAMA_CONFIG or ~/.config/otedama/config.yaml).")
+    return fs
+
+
+def cmd_pool(args: list[str], stdout: TextIO, stderr: TextIO) -> int:
+    fs = pool_flags(stderr)
     rc = parse_subcommand(fs, args, stdout, stderr)
     if rc is not None:
         return rc
@@ -88,6 +119,10 @@ def cmd_pool(args: list[str], stdout: TextIO, stderr: TextIO) -> int:
         if err:
             stderr.write(f"pool: payout address invalid: {err}\n")
             return EXIT_CONFIG
+    err = verify_options_error(verify_options(fs))
+    if err:
+        stderr.write(f"pool: {err}\n")
+        return EXIT_CONFIG
     if fs["noise-suite"] not in ("", "ellswift", "legacy"):
         stderr.write("pool: --noise-suite must be ellswift or legacy (empty accepts both)\n")
         return EXIT_CONFIG
@@ -127,7 +162,7 @@ async def _serve(fs, algos: list[str], stdout: TextIO) -> int:
                            journal_path=journal or ":memory:", payout_scheme=fs["payout-scheme"],
                            dialect=fs["dialect"], noise=fs["sv2-noise"], noise_suite=fs["noise-suite"],
                            coinbase_message=fs.values.get("coinbase-message", PoolOptions.coinbase_message),
-                           noise_authority_secret=int(fs["noise-authority-key"] or "0", 16))
+                           noise_authority_secret=int(fs["noise-authority-key"] or "0", 16), **verify_options(fs))
 
         def log(level, msg):
             stdout.write(f"[{level}] {msg}\n")

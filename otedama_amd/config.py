@@ -94,6 +94,11 @@ class PoolServerConfig:
     vardiff_retarget_seconds: float = 30.0
     journal_path: str = ""
     coinbase_message: str = "/otedama-mi355x/"
+    # micro-batched share validation (pool/microbatch.py); "" = off
+    verify_device: str = ""             # "", "cpu" or "cuda:N"
+    verify_batch_ms: float = 2.0        # flush this long after the oldest pending submit
+    verify_batch_max: int = 4096        # flush at this many pending submits
+    verify_min_gpu: int = 0             # fewer survivors than this are hashed on the CPU; 0 = per-algorithm default
 
 
 @dataclass
@@ -176,6 +181,17 @@ class Config:
             issues.append("pool_server.initial_difficulty must be > 0")
         if self.pool_server.target_share_seconds <= 0:
             issues.append("pool_server.target_share_seconds must be > 0")
+        ps = self.pool_server
+        from otedama_amd.pool.microbatch import valid_device  # torch-free; the one statement of the device grammar
+
+        if not valid_device(str(ps.verify_device)):
+            issues.append(f"pool_server.verify_device {ps.verify_device!r} is not one of \"\", cpu, cuda:N")
+        if ps.verify_batch_ms <= 0:
+            issues.append("pool_server.verify_batch_ms must be > 0")
+        if ps.verify_batch_max <= 0:
+            issues.append("pool_server.verify_batch_max must be > 0")
+        if ps.verify_min_gpu < 0:
+            issues.append("pool_server.verify_min_gpu must be >= 0 (0 = the algorithm's default)")
         if issues:
             raise ConfigError("config validation failed:\n  - " + "\n  - ".join(issues))
 

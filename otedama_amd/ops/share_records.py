@@ -19,6 +19,11 @@ VERDICT_BAD_INDEX = 0x80  # index outside the target table; no other bit is set
 
 _REC = struct.Struct("<16sIIII")
 
+# The 128-byte result record of the live path (``ShareResult``): bytes 0..79 the header, 80..111 the hash, 112 the
+# verdict byte, 113..127 zero.
+RESULT_BYTES = 128
+_RES = struct.Struct("<80s32sB15x")
+
 
 def pack_records(shares: Sequence[tuple], target_indices: Sequence[int], en_size: int) -> bytes:
     """``shares``: ``(extranonce, ntime, nonce, version)`` tuples, every extranonce exactly ``en_size`` bytes (a
@@ -50,3 +55,16 @@ def unpack_records(records: bytes, en_size: int) -> tuple[list[tuple], list[int]
         shares.append((en[:en_size], ntime, nonce, version))
         indices.append(idx)
     return shares, indices
+
+
+def unpack_results(raw, n: int | None = None) -> list[tuple[bytes, bytes, int]]:
+    """Result records (bytes, bytearray or memoryview; the first ``n`` if given) -> ``(header, hash, verdict byte)``
+    per share, the list ``pool.batch.check_shares`` returns."""
+    view = memoryview(raw)
+    if n is not None:
+        if n < 0 or n * RESULT_BYTES > len(view):
+            raise ValueError(f"{n} result records do not fit {len(view)} bytes")
+        view = view[:n * RESULT_BYTES]
+    if len(view) % RESULT_BYTES:
+        raise ValueError(f"results must be a multiple of {RESULT_BYTES} bytes")
+    return list(_RES.iter_unpack(view))

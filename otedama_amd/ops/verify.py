@@ -9,8 +9,12 @@ the digest ops (:mod:`otedama_amd.ops.digest`):
   2. the ``HeaderDigest`` launches of the op's algorithm
   3. ``otd_share_verdict``  the 256-bit little-endian compare against per-share targets and the network target
 
-Layouts of the job block and the share record: csrc/include/otedama/share_job.h. The record packer is torch-free
-(:mod:`otedama_amd.ops.share_records`) and re-exported here.
+For a pool's live micro-batches, :meth:`ShareVerify.launch_results` ends the same chain with ``otd_share_pack``
+(csrc/kernels/share_results.hip) instead: one packed 128-byte record per share (header, hash, verdict), so that
+:meth:`ShareVerify.results` moves one pinned buffer in and one out.
+
+Layouts of the job block, the share record and the result record: csrc/include/otedama/share_job.h. The record
+packer is torch-free (:mod:`otedama_amd.ops.share_records`) and re-exported here.
 """
 from __future__ import annotations
 
@@ -20,8 +24,9 @@ from typing import Sequence
 import torch
 
 from otedama_amd.ops.digest import ALIGN, DIGEST_BYTES, HEADER_BYTES, HeaderDigest
-from otedama_amd.ops.share_records import (MAX_EXTRANONCE, RECORD_BYTES, VERDICT_BAD_INDEX, VERDICT_NETWORK,  # noqa: F401
-                                           VERDICT_SHARE, pack_records, unpack_records)
+from otedama_amd.ops.share_records import (MAX_EXTRANONCE, RECORD_BYTES, RESULT_BYTES, VERDICT_BAD_INDEX,  # noqa: F401
+                                           VERDICT_NETWORK, VERDICT_SHARE, pack_records, unpack_records,
+                                           unpack_results)
 
 TARGET_BYTES = 32
 
@@ -44,6 +49,13 @@ class ShareVerify:
         self.device = self.digest.device
         self.headers: torch.Tensor | None = None  # uint8 [rows, 80], grown to the largest batch seen
         self._last_stream = None
+        # the live path (launch_results / results): the digests between the chain and the pack kernel, and the
+        # staging buffers of results(), all grown to the largest batch seen
+        self._digests: torch.Tensor | None = None
+        self._pin_in: torch.Tensor | None = None   # pinned: records | targets
+        self._dev_in: torch.Tensor | None = None
+        self._pin_out: torch.Tensor | None = None  # pinned: result records
+        self._dev_out: torch.Tensor | None = None
 
     def prepare(self, coinb1: bytes, coinb2: bytes, en_size: int, prev_hash: bytes, nbits: int,
                 branches: Sequence[bytes]) -> PreparedJob:
@@ -113,6 +125,93 @@ class ShareVerify:
         self.native.launch_share_verdict(job.dev.data_ptr(), records.data_ptr(), digests.data_ptr(),
                                          targets.data_ptr(), targets.shape[0], n, verdicts.data_ptr(), s)
         return verdicts, digests, headers
+
+    def launch_results(self, job: PreparedJob, records: torch.Tensor, targets: torch.Tensor,
+                       out: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """The live form of :meth:`launch`: the same arguments, checks and stream handling, one packed 128-byte
+        result record per share (header 80 | hash 32 | verdict 1 | zeros 15; ``ShareResult`` in share_job.h) as
+        uint8 ``[n, 128]`` (``out`` if given: that shape, contiguous, 16-byte aligned, on the op's device), without
+        synchronising: ``otd_share_headers``, the digest launches of the algorithm, then ``otd_share_pack``
+        (csrc/kernels/share_results.hip), which compares and packs. An empty batch returns an empty tensor and
+        enqueues nothing."""
+        n = self._check(job, records, targets)
+        if out is not None:
+            if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, RESULT_BYTES)
+                    or out.device != self.device):
+                raise ValueError(f"out must be a uint8 [n, {RESULT_BYTES}] tensor on {self.device}")
+            if not out.is_contiguous() or (n and out.data_ptr() % ALIGN):
+                raise ValueError(f"out must be contiguous and start at a {ALIGN}-byte aligned address")
+        if n == 0:
+            return out if out is not None else torch.empty((0, RESULT_BYTES), dtype=torch.uint8, device=self.device)
+        cur = torch.cuda.current_stream(self.device)
+        if stream is None:
+            stream = cur
+        elif stream != cur:
+            stream.wait_stream(cur)  # the caller produced `records` and `targets` on the current stream
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = torch.empty((n, RESULT_BYTES), dtype=torch.uint8, device=self.device)
+        s = stream.cuda_stream
+        if self._last_stream is not None and self._last_stream != stream:
+            stream.wait_stream(self._last_stream)  # headers and digests are still in use by the previous launch
+        if self.headers is None or self.headers.shape[0] < n:
+            if self.headers is not None and self._last_stream is not None:
+                self.headers.record_stream(self._last_stream)
+            with torch.cuda.stream(stream):
+                self.headers = torch.empty((n, HEADER_BYTES), dtype=torch.uint8, device=self.device)
+        if self._digests is None or self._digests.shape[0] < n:
+            if self._digests is not None and self._last_stream is not None:
+                self._digests.record_stream(self._last_stream)
+            with torch.cuda.stream(stream):
+                self._digests = torch.empty((n, DIGEST_BYTES), dtype=torch.uint8, device=self.device)
+        self._last_stream = stream
+        headers, digests = self.headers[:n], self._digests[:n]
+        self.native.launch_share_headers(job.dev.data_ptr(), records.data_ptr(), n, headers.data_ptr(), s)
+        self.digest.launch(headers, out=digests, stream=stream)
+        self.native.launch_share_pack(job.dev.data_ptr(), records.data_ptr(), headers.data_ptr(), digests.data_ptr(),
+                                      targets.data_ptr(), targets.shape[0], n, out.data_ptr(), s)
+        return out
+
+    def _grown(self, name: str, nbytes: int, pinned: bool) -> torch.Tensor:
+        buf = getattr(self, name)
+        if buf is None or buf.numel() < nbytes:
+            size = max(nbytes, 2 * buf.numel() if buf is not None else 4096)
+            buf = (torch.empty(size, dtype=torch.uint8, pin_memory=True) if pinned
+                   else torch.empty(size, dtype=torch.uint8, device=self.device))
+            setattr(self, name, buf)
+        return buf
+
+    def results(self, job: PreparedJob, shares: Sequence[tuple], targets: Sequence[bytes],
+                target_indices: Sequence[int] | None = None) -> list[tuple[bytes, bytes, int]]:
+        """The live entry: ``(extranonce, ntime, nonce, version)`` tuples and 32-byte targets in, ``(header, hash,
+        verdict byte)`` per share out, the list ``pool.batch.check_shares`` returns. One pinned buffer (records |
+        targets) goes to the device and one pinned buffer of result records comes back, both copies non-blocking on
+        the current stream around :meth:`launch_results`, then one stream synchronise. The four buffers are the op's
+        own and grow to the largest batch seen; the call is not re-entrant."""
+        targets = [bytes(t) for t in targets]
+        if not targets or any(len(t) != TARGET_BYTES for t in targets):
+            raise ValueError(f"need at least one target, each {TARGET_BYTES} bytes")
+        if target_indices is None:
+            target_indices = [0] * len(shares)
+        packed = pack_records(shares, target_indices, job.en_size)
+        n = len(shares)
+        if n == 0:
+            return []
+        rec_bytes, out_bytes = n * RECORD_BYTES, n * RESULT_BYTES
+        in_bytes = rec_bytes + len(targets) * TARGET_BYTES
+        pin_in, dev_in = self._grown("_pin_in", in_bytes, True), self._grown("_dev_in", in_bytes, False)
+        pin_out, dev_out = self._grown("_pin_out", out_bytes, True), self._grown("_dev_out", out_bytes, False)
+        host = memoryview(pin_in.numpy())
+        host[:rec_bytes] = packed
+        host[rec_bytes:in_bytes] = b"".join(targets)
+        stream = torch.cuda.current_stream(self.device)
+        dev_in[:in_bytes].copy_(pin_in[:in_bytes], non_blocking=True)
+        out = dev_out[:out_bytes].view(n, RESULT_BYTES)
+        self.launch_results(job, dev_in[:rec_bytes].view(n, RECORD_BYTES),
+                            dev_in[rec_bytes:in_bytes].view(len(targets), TARGET_BYTES), out=out)
+        pin_out[:out_bytes].copy_(dev_out[:out_bytes], non_blocking=True)
+        stream.synchronize()
+        return unpack_results(memoryview(pin_out.numpy())[:out_bytes])
 
     def verify(self, job: PreparedJob, shares: Sequence[tuple], targets: Sequence[bytes],
                target_indices: Sequence[int] | None = None) -> tuple[list[int], list[bytes], list[bytes]]:

@@ -77,6 +77,13 @@ class PoolOptions:
     noise_authority_secret: int = 0
     noise_cert_seconds: int = 365 * 86400
     noise_suite: str = ""  # "" = accept both suites (by message 1's length); "ellswift" | "legacy" = only that one
+    # Micro-batched validation (pool/microbatch.py). "" = off: validate_async hashes every submit on its own, as
+    # before. "cpu": concurrent submits are collected and hashed per batch on one worker thread. "cuda:N": the batch
+    # is verified on that GPU (ops.verify.ShareVerify.results).
+    verify_device: str = ""
+    verify_batch_ms: float = 2.0   # flush this long after the oldest pending submit (the wait added to a lone share)
+    verify_batch_max: int = 4096   # flush at this many pending submits (bounds the pinned staging memory)
+    verify_min_gpu: int = 0        # a flush with fewer survivors is hashed on the CPU; 0 = the algorithm's default
 
 
 @dataclass
@@ -191,6 +198,10 @@ class PoolServer:
         # CLOCK_MONOTONIC time each new block's clean job was handed to every connection (a node's job-switch probe
         # times each rank's device from here: parallel/node_probe.py)
         self.new_block_at: deque = deque(maxlen=256)
+        # the micro-batcher, made by the first validate_async when opts.verify_device is set; `verify_hasher`
+        # replaces its device path (tests inject one; None = ShareVerify.results on opts.verify_device)
+        self._batcher = None
+        self.verify_hasher = None
         self._init_metrics(registry)
 
     # ------------------------------------------------------------ metrics
@@ -246,6 +257,8 @@ class PoolServer:
                 await asyncio.wait_for(s.wait_closed(), 2)
             except asyncio.TimeoutError:
                 pass
+        if self._batcher is not None:
+            await self._batcher.close()  # pending submits are answered (on the CPU) before the journal closes
         self._hash_pool.shutdown(wait=False, cancel_futures=True)
         self.journal.close()
 
@@ -350,6 +363,12 @@ class PoolServer:
         """validate() with the header hash off the event loop for slow algorithms (scrypt: ~ms per share,
         GIL released), so a burst of shares from many GPUs does not stall every other connection."""
         t0 = time.perf_counter()
+        if self.opts.verify_device:  # micro-batched: the wait for the flush is part of submit received -> verdict
+            v = await self._get_batcher().submit((worker, job_id, extranonce, ntime, nonce, version), t0)
+            ms = (time.perf_counter() - t0) * 1e3
+            self._validate_ms.append(ms)
+            self._validate_log.append((time.monotonic(), ms))
+            return v
         pre = self._precheck(worker, job_id, extranonce, ntime, nonce, version)
         if isinstance(pre, Verdict):
             v = pre
@@ -369,34 +388,63 @@ class PoolServer:
         """validate() over a batch: ``items`` are ``(worker, job_id, extranonce, ntime, nonce, version)``. The
         verdicts, counters, reject reasons and journal rows are those of validate() on the items in order (in-batch
         duplicates and a block found mid-batch included); the headers and hashes of the shares that pass the field
-        checks are computed per distinct job in one ``pool.batch.check_shares`` call: on the CPU (``device=None``) or
-        as one GPU batch (``device="cuda:0"``). The difficulty, grace and block logic stays in _finish, on the
-        returned hashes."""
-        from otedama_amd.pool.batch import ShareJob, check_shares
+        checks are computed per distinct op input in one ``pool.batch.check_shares`` call: on the CPU
+        (``device=None``) or as one GPU batch (``device="cuda:0"``). The difficulty, grace and block logic stays in
+        _finish, on the returned hashes."""
+        from otedama_amd.pool.batch import check_shares
 
-        # 1. field checks in order; nothing is counted or journalled yet, so the rows keep the order of the items
-        checked = [self._field_check(w, job_id, ntime, version) for w, job_id, _en, ntime, _nonce, version in items]
-        # 2. headers and hashes of the survivors, one call per distinct job (and extranonce length)
-        groups: dict[tuple[int, int], list[int]] = {}
+        checked = self._check_fields(items)
+        hashed = self._hash_groups(self._group_survivors(items, checked),
+                                   lambda sj, shares, targets, tidx: check_shares(self.algo.name, sj, shares, targets,
+                                                                                  tidx, device))
+        return self._finish_many(items, checked, hashed)
+
+    # The three stages of validate_many. The micro-batcher (pool/microbatch.py) runs 1 and 3 on the event loop and
+    # _hash_groups, which touches nothing of the pool but its algorithm, on its worker thread.
+    def _check_fields(self, items: list) -> list:
+        """1. field checks in order; nothing is counted or journalled yet, so the rows keep the order of the items."""
+        return [self._field_check(w, job_id, ntime, version) for w, job_id, _en, ntime, _nonce, version in items]
+
+    def _group_survivors(self, items: list, checked: list) -> list:
+        """The shares that passed the field checks as ``(ShareJob, item indices, shares, targets, target indices)``
+        groups, one per distinct input of the share-verification op: coinbase parts, branches, prev_hash, nbits and
+        extranonce length. Not per job id: every job of one block shares all of these (see _precheck), so a live
+        batch over several job ids is still one launch."""
+        from otedama_amd.pool.batch import ShareJob
+
+        groups: dict[tuple, list[int]] = {}
         for i, (job, item) in enumerate(zip(checked, items)):
             if not isinstance(job, str):
-                groups.setdefault((job.job_int, len(item[2])), []).append(i)
-        hashed: dict[int, tuple[bytes, bytes]] = {}
-        for (_job_int, en_size), idxs in groups.items():
-            job = checked[idxs[0]]
-            sj = ShareJob(job.coinb1, job.coinb2, en_size, job.block.prev_hash, job.block.nbits, job.branches)
+                key = (job.coinb1, job.coinb2, tuple(job.branches), job.block.prev_hash, job.block.nbits, len(item[2]))
+                groups.setdefault(key, []).append(i)
+        plan = []
+        for (coinb1, coinb2, branches, prev_hash, nbits, en_size), idxs in groups.items():
+            sj = ShareJob(coinb1, coinb2, en_size, prev_hash, nbits, list(branches))
             table: dict[bytes, int] = {}
             tidx = [table.setdefault(self.share_target(items[i][0].vd.difficulty), len(table)) for i in idxs]
             shares = [(items[i][2], items[i][3], items[i][4], items[i][5]) for i in idxs]
-            if 1 <= en_size <= 16:
-                res = check_shares(self.algo.name, sj, shares, list(table), tidx, device)
-                for i, (hdr, h, _bits) in zip(idxs, res):
+            plan.append((sj, idxs, shares, list(table), tidx))
+        return plan
+
+    def _hash_groups(self, plan: list, hasher) -> dict:
+        """2. headers and hashes of the survivors, one ``hasher(job, shares, targets, target_indices)`` call (the
+        signature and result of ``pool.batch.check_shares`` without its algorithm) per group: item index ->
+        ``(header, hash)``."""
+        from otedama_amd.pool.batch import header_of
+
+        hashed: dict[int, tuple[bytes, bytes]] = {}
+        for sj, idxs, shares, targets, tidx in plan:
+            if 1 <= sj.en_size <= 16:
+                for i, (hdr, h, _bits) in zip(idxs, hasher(sj, shares, targets, tidx)):
                     hashed[i] = (hdr, h)
             else:  # no such extranonce in the job block's record: one at a time, as validate() does
                 for i, (en, ntime, nonce, version) in zip(idxs, shares):
-                    hdr = self.header_for(job, en, version, ntime, nonce)
+                    hdr = header_of(sj, en, ntime, nonce, version)
                     hashed[i] = (hdr, self.algo.hash(hdr))
-        # 3. verdicts in order: _finish repeats the stale and duplicate checks of _precheck
+        return hashed
+
+    def _finish_many(self, items: list, checked: list, hashed: dict) -> list[Verdict]:
+        """3. verdicts in order: _finish repeats the stale and duplicate checks of _precheck."""
         out = []
         for i, (job, item) in enumerate(zip(checked, items)):
             worker, job_id = item[0], item[1]
@@ -406,6 +454,13 @@ class PoolServer:
                 hdr, h = hashed[i]
                 out.append(self._finish(worker, job_id, job, hdr, h))
         return out
+
+    def _get_batcher(self):
+        if self._batcher is None:
+            from otedama_amd.pool.microbatch import ShareBatcher
+
+            self._batcher = ShareBatcher(self, device_hasher=self.verify_hasher)
+        return self._batcher
 
     def share_target(self, difficulty: float) -> bytes:
         """Share target for a difficulty, clamped to 2^256-1 (below ~diff1/2^256 the target would overflow)."""
@@ -559,6 +614,14 @@ class PoolServer:
         return {"window_shares": n, "window_ratio": dstar / w.vd.difficulty if dstar else None,
                 "settled": self.vardiff.settled(w.vd, mutate=False)}
 
+    def verify_stats(self) -> dict:
+        """The ``verify`` object of /api/v1/pool: the micro-batcher's device, whether the configured path is in use
+        (False when the feature is off, and after a device error has turned a GPU path off), and its counters."""
+        if self._batcher is not None:
+            return self._batcher.stats()
+        return {"device": self.opts.verify_device, "enabled": False, "batches": 0, "gpu_shares": 0, "cpu_shares": 0,
+                "last_batch": 0, "max_batch": 0, "device_errors": 0}
+
     def stats(self) -> dict:
         now = time.monotonic()
         live = self._live_workers()
@@ -572,6 +635,7 @@ class PoolServer:
             "validate_ms": {"p50": self.validation_ms(0.5), "p95": self.validation_ms(0.95),
                             "p99": self.validation_ms(0.99), "samples": len(self._validate_ms)},
             "fixed_difficulty": self.opts.fixed_difficulty,
+            "verify": self.verify_stats(),
             "new_block_at": list(self.new_block_at)[-64:],
             # per live connection: the difficulty in force, how often vardiff moved it, and when it last moved
             # (seconds after the channel opened: the time vardiff took to reach the difficulty it holds)
