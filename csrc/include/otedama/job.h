@@ -91,5 +91,10 @@ constexpr int kScryptCoop = 8;
 constexpr int kScryptLaneW8 = 9;   // per-lane ROMix, gap 1, pinned to 8 waves/SIMD
 constexpr int kScryptCoop2 = 11;   // cooperative ROMix, two software-pipelined hashes per lane (gap 1)
 constexpr int kScryptCoopSplit = 12;  // cooperative ROMix, write and lookup phases as two launches (gap 1)
+// Every code above and no other.
+constexpr bool scrypt_gap_valid(int gap) {
+  return gap == 1 || gap == 2 || gap == 4 || gap == kScryptCoop || gap == kScryptLaneW8 || gap == kScryptCoop2 ||
+         gap == kScryptCoopSplit;
+}
 
 }  // namespace otedama

@@ -19,9 +19,9 @@ int gpu_device_count();
 std::string gpu_arch_name(int device);
 int gpu_cu_count(int device);
 
-// Launches for the Python ops layer (gpu_miner.hip; torch-owned buffers and streams): pointers and the stream arrive
-// as integers, a HIP error is thrown as std::runtime_error. Hits go to the legacy device-memory slots after out[0];
-// no abort word.
+// Launches for the Python ops layer (all in runtime/ops_launch.hip; torch-owned buffers and streams): pointers and
+// the stream arrive as integers, a HIP error is thrown as std::runtime_error. Searches: hits go to the legacy
+// device-memory slots after out[0]; no abort word.
 void py_launch_sha256d(const Sha256dParams& p, uint32_t base, uint64_t count, uintptr_t out, uint32_t cap, int grid,
                        uintptr_t stream);
 void py_launch_sha256d_k(const Sha256dParamsK& p, uint32_t base, uint64_t count, uintptr_t out, uint32_t cap, int grid,
@@ -35,7 +35,7 @@ void py_launch_x11_stage(const X11Params& p, int stage, uint32_t base, uintptr_t
 void py_launch_x11(const X11Params& p, uint32_t base, uintptr_t H, uint32_t stride, uint32_t n, uintptr_t out,
                    uint32_t cap, uintptr_t stream);
 
-// Digest ops (digest_batch.hip): n unrelated 80-byte headers at headers + 80 * i -> n digests at out + 32 * i, in
+// Digest ops (kernels in digest_batch.hip): n unrelated 80-byte headers at headers + 80 * i -> n digests at out + 32 * i, in
 // the byte order PowAlgorithm.hash returns. Same conventions as above; both arrays must be 16-byte aligned.
 void py_launch_sha256d_digest(uintptr_t headers, uint32_t n, uintptr_t out, uintptr_t stream);
 void py_launch_scrypt_digest(uintptr_t headers, uint32_t n, uintptr_t xbuf, uintptr_t scratch, int gap, uintptr_t out,
@@ -43,15 +43,15 @@ void py_launch_scrypt_digest(uintptr_t headers, uint32_t n, uintptr_t xbuf, uint
 void py_launch_x11_digest(uintptr_t headers, uintptr_t H, uint32_t stride, uint32_t n, uintptr_t out,
                           uintptr_t stream);
 
-// Share verification (share_verify.hip; layouts in otedama/share_job.h): n 32-byte share records against one
+// Share verification (kernels in share_verify.hip; layouts in otedama/share_job.h): n 32-byte share records against one
 // uploaded job block -> n 80-byte headers, and n digests against a table of n_targets 32-byte targets -> n verdict
 // bytes. Same conventions as above; every array but the verdicts must be 16-byte aligned.
 void py_launch_share_headers(uintptr_t job, uintptr_t records, uint32_t n, uintptr_t headers, uintptr_t stream);
 void py_launch_share_verdict(uintptr_t job, uintptr_t records, uintptr_t digests, uintptr_t targets,
                              uint32_t n_targets, uint32_t n, uintptr_t verdicts, uintptr_t stream);
 
-// Live share verification (share_results.hip): the headers and digests of the chain above -> n 128-byte ShareResult
-// records, with the compares done there. Every array is 16-byte aligned.
+// Live share verification (otd_share_pack of share_verify.hip): the headers and digests of the chain above -> n
+// 128-byte ShareResult records, with the compares done there. Every array is 16-byte aligned.
 void py_launch_share_pack(uintptr_t job, uintptr_t records, uintptr_t headers, uintptr_t digests, uintptr_t targets,
                           uint32_t n_targets, uint32_t n, uintptr_t results, uintptr_t stream);
 

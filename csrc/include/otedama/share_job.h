@@ -30,7 +30,8 @@ constexpr uint8_t kVerdictShare = 1;      // hash <= targets[target_index]
 constexpr uint8_t kVerdictNetwork = 2;    // hash <= the network target of nbits
 constexpr uint8_t kVerdictBadIndex = 0x80;  // target_index outside the table; no other bit is set
 
-// One verified share, as the live path returns it (csrc/kernels/share_results.hip): eight 16-byte stores.
+// One verified share, as the live path returns it (otd_share_pack of csrc/kernels/share_verify.hip): eight 16-byte
+// stores.
 struct alignas(16) ShareResult {
   uint8_t header[80];  // the bytes otd_share_headers writes
   uint8_t hash[32];    // the algorithm's hash of the header

@@ -18,11 +18,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <stdexcept>
-#include <string>
 
 #include "cdna_bitops.h"
 #include "scrypt_pbkdf_dev.h"
+#include "otedama/hip_check.h"
 #include "otedama/job.h"
 #include "otedama/search_launch.h"
 #include "otedama/x11.h"
@@ -115,10 +114,6 @@ extern "C" __global__ __launch_bounds__(256) void otd_x11_gather_digest(const ui
 
 namespace otedama {
 
-static bool aligned16(const void* a, const void* b) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
-}
-
 hipError_t launch_sha256d_digest(const uint8_t* headers, uint32_t n, uint8_t* out, hipStream_t s) {
   if (n == 0 || !headers || !out || !aligned16(headers, out)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(otd_sha256d_digest, dim3((n + 255u) / 256u), dim3(256), 0, s,
@@ -133,10 +128,7 @@ hipError_t launch_scrypt_digest(const uint8_t* headers, uint32_t n, void* xbuf, 
                                 int grid, hipStream_t stream) {
   if (n == 0 || grid <= 0 || uint64_t(n) > uint64_t(grid) * 256u || !headers || !xbuf || !scratch || !out)
     return hipErrorInvalidValue;
-  if (gap != 1 && gap != 2 && gap != 4 && gap != kScryptCoop && gap != kScryptLaneW8 && gap != kScryptCoop2 &&
-      gap != kScryptCoopSplit)
-    return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(headers) | reinterpret_cast<uintptr_t>(out)) & 15u) return hipErrorInvalidValue;
+  if (!scrypt_gap_valid(gap) || !aligned16(headers, out)) return hipErrorInvalidValue;
   const uint4* H = reinterpret_cast<const uint4*>(headers);
   uint4* X = static_cast<uint4*>(xbuf);
   const int eg = int((n + 255) / 256);
@@ -159,32 +151,6 @@ hipError_t launch_x11_digest(const uint8_t* headers, uint64_t* H, uint32_t strid
   hipLaunchKernelGGL(otd_x11_gather_digest, dim3((n + 255u) / 256u), dim3(256), 0, s,
                      static_cast<const uint64_t*>(H), stride, n, reinterpret_cast<uint4*>(out));
   return hipGetLastError();
-}
-
-// Launches for the Python ops layer (torch-owned buffers and streams).
-static void check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(e) + " at " + what);
-}
-
-void py_launch_sha256d_digest(uintptr_t headers, uint32_t n, uintptr_t out, uintptr_t stream) {
-  check(launch_sha256d_digest(reinterpret_cast<const uint8_t*>(headers), n, reinterpret_cast<uint8_t*>(out),
-                              reinterpret_cast<hipStream_t>(stream)),
-        "launch_sha256d_digest");
-}
-
-void py_launch_scrypt_digest(uintptr_t headers, uint32_t n, uintptr_t xbuf, uintptr_t scratch, int gap, uintptr_t out,
-                             int grid, uintptr_t stream) {
-  check(launch_scrypt_digest(reinterpret_cast<const uint8_t*>(headers), n, reinterpret_cast<void*>(xbuf),
-                             reinterpret_cast<void*>(scratch), gap, reinterpret_cast<uint8_t*>(out), grid,
-                             reinterpret_cast<hipStream_t>(stream)),
-        "launch_scrypt_digest");
-}
-
-void py_launch_x11_digest(uintptr_t headers, uintptr_t H, uint32_t stride, uint32_t n, uintptr_t out,
-                          uintptr_t stream) {
-  check(launch_x11_digest(reinterpret_cast<const uint8_t*>(headers), reinterpret_cast<uint64_t*>(H), stride, n,
-                          reinterpret_cast<uint8_t*>(out), reinterpret_cast<hipStream_t>(stream)),
-        "launch_x11_digest");
 }
 
 }  // namespace otedama

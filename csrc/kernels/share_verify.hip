@@ -7,6 +7,13 @@
 //   otd_share_verdict  digests -> one verdict byte per share: the 256-bit little-endian compare (byte 31 most
 //                      significant, le256_leq of otedama/sha256.h) against the share's target and the job's network
 //                      target.
+//   otd_share_pack     the live path's last step instead of otd_share_verdict: headers + digests -> one packed
+//                      128-byte ShareResult per share, so a pool's micro-batch is one buffer in and one buffer out.
+//                      Per lane: the same two compares (share_compare_dev.h), then the record as eight 16-byte
+//                      stores (header 5, hash 2, verdict and zeros 1). Every algorithm goes through it. A
+//                      single-launch SHA-256d kernel (header build, SHA-256d and compares in registers) was built and
+//                      measured against this chain and did not earn its place: docs/KERNELS.md, "Live share
+//                      verification". It is not in the tree.
 //
 // Everything that comes from the job block is the same for every lane: the template words, the branches, the
 // midstate and the counts are read through indices formed from kernel arguments and loop counters only, so they are
@@ -15,10 +22,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <stdexcept>
-#include <string>
 
 #include "cdna_bitops.h"
+#include "share_compare_dev.h"
+#include "otedama/hip_check.h"
 #include "otedama/search_launch.h"
 #include "otedama/share_job.h"
 
@@ -155,16 +162,6 @@ extern "C" __global__ __launch_bounds__(256) void otd_share_headers(const ShareJ
   h[4] = make_uint4(root[7], r1.x, job->nbits, r1.y);
 }
 
-namespace {
-// a <= b for 256-bit values as little-endian words, word 7 most significant: the highest differing word decides.
-__device__ __forceinline__ bool leq256(const uint32_t a[8], const uint32_t b[8]) {
-  bool r = true;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) r = a[w] != b[w] ? a[w] < b[w] : r;
-  return r;
-}
-}  // namespace
-
 extern "C" __global__ __launch_bounds__(256) void otd_share_verdict(const ShareJobBlock* __restrict__ job,
                                                                     const uint4* __restrict__ recs,
                                                                     const uint4* __restrict__ digests,
@@ -179,24 +176,41 @@ extern "C" __global__ __launch_bounds__(256) void otd_share_verdict(const ShareJ
     return;
   }
   const uint4 d0 = digests[2 * uint64_t(i)], d1 = digests[2 * uint64_t(i) + 1];
-  const uint4 t0 = targets[2 * uint64_t(idx)], t1 = targets[2 * uint64_t(idx) + 1];
-  const uint32_t d[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
-  const uint32_t t[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-  uint32_t net[8];
-#pragma unroll
-  for (int w = 0; w < 8; ++w) net[w] = job->net_target[w];
-  verdicts[i] = uint8_t((leq256(d, t) ? otedama::kVerdictShare : 0) | (leq256(d, net) ? otedama::kVerdictNetwork : 0));
+  verdicts[i] = uint8_t(share_verdict_bits(job, targets, idx, d0, d1));
+}
+
+static_assert(sizeof(otedama::ShareResult) == 8 * sizeof(uint4), "a result record is eight 16-byte stores");
+
+extern "C" __global__ __launch_bounds__(256) void otd_share_pack(const ShareJobBlock* __restrict__ job,
+                                                                 const uint4* __restrict__ recs,
+                                                                 const uint4* __restrict__ headers,
+                                                                 const uint4* __restrict__ digests,
+                                                                 const uint4* __restrict__ targets,
+                                                                 uint32_t n_targets, uint32_t n,
+                                                                 uint4* __restrict__ results) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t idx = recs[2 * uint64_t(i) + 1].w;
+  const uint4* h = headers + uint64_t(i) * 5u;
+  const uint4 h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3], h4 = h[4];
+  const uint4 d0 = digests[2 * uint64_t(i)], d1 = digests[2 * uint64_t(i) + 1];
+  uint32_t verdict = otedama::kVerdictBadIndex;
+  if (idx < n_targets) verdict = share_verdict_bits(job, targets, idx, d0, d1);  // the guard, as above
+  uint4* o = results + uint64_t(i) * 8u;
+  o[0] = h0;
+  o[1] = h1;
+  o[2] = h2;
+  o[3] = h3;
+  o[4] = h4;
+  o[5] = d0;
+  o[6] = d1;
+  o[7] = make_uint4(verdict, 0u, 0u, 0u);
 }
 
 namespace otedama {
 
-static bool aligned16(uintptr_t a) { return (a & 15u) == 0; }
-
 hipError_t launch_share_headers(const void* job, const uint8_t* records, uint32_t n, uint8_t* headers, hipStream_t s) {
-  if (n == 0 || !job || !records || !headers) return hipErrorInvalidValue;
-  if (!aligned16(reinterpret_cast<uintptr_t>(job) | reinterpret_cast<uintptr_t>(records) |
-                 reinterpret_cast<uintptr_t>(headers)))
-    return hipErrorInvalidValue;
+  if (n == 0 || !job || !records || !headers || !aligned16(job, records, headers)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(otd_share_headers, dim3((n + 255u) / 256u), dim3(256), 0, s,
                      static_cast<const ShareJobBlock*>(job), reinterpret_cast<const uint4*>(records), n,
                      reinterpret_cast<uint4*>(headers));
@@ -206,9 +220,7 @@ hipError_t launch_share_headers(const void* job, const uint8_t* records, uint32_
 hipError_t launch_share_verdict(const void* job, const uint8_t* records, const uint8_t* digests, const uint8_t* targets,
                                 uint32_t n_targets, uint32_t n, uint8_t* verdicts, hipStream_t s) {
   if (n == 0 || n_targets == 0 || !job || !records || !digests || !targets || !verdicts) return hipErrorInvalidValue;
-  if (!aligned16(reinterpret_cast<uintptr_t>(job) | reinterpret_cast<uintptr_t>(records) |
-                 reinterpret_cast<uintptr_t>(digests) | reinterpret_cast<uintptr_t>(targets)))
-    return hipErrorInvalidValue;
+  if (!aligned16(job, records, digests, targets)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(otd_share_verdict, dim3((n + 255u) / 256u), dim3(256), 0, s,
                      static_cast<const ShareJobBlock*>(job), reinterpret_cast<const uint4*>(records),
                      reinterpret_cast<const uint4*>(digests), reinterpret_cast<const uint4*>(targets), n_targets, n,
@@ -216,23 +228,17 @@ hipError_t launch_share_verdict(const void* job, const uint8_t* records, const u
   return hipGetLastError();
 }
 
-static void check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(e) + " at " + what);
-}
-
-void py_launch_share_headers(uintptr_t job, uintptr_t records, uint32_t n, uintptr_t headers, uintptr_t stream) {
-  check(launch_share_headers(reinterpret_cast<const void*>(job), reinterpret_cast<const uint8_t*>(records), n,
-                             reinterpret_cast<uint8_t*>(headers), reinterpret_cast<hipStream_t>(stream)),
-        "launch_share_headers");
-}
-
-void py_launch_share_verdict(uintptr_t job, uintptr_t records, uintptr_t digests, uintptr_t targets,
-                             uint32_t n_targets, uint32_t n, uintptr_t verdicts, uintptr_t stream) {
-  check(launch_share_verdict(reinterpret_cast<const void*>(job), reinterpret_cast<const uint8_t*>(records),
-                             reinterpret_cast<const uint8_t*>(digests), reinterpret_cast<const uint8_t*>(targets),
-                             n_targets, n, reinterpret_cast<uint8_t*>(verdicts),
-                             reinterpret_cast<hipStream_t>(stream)),
-        "launch_share_verdict");
+hipError_t launch_share_pack(const void* job, const uint8_t* records, const uint8_t* headers, const uint8_t* digests,
+                             const uint8_t* targets, uint32_t n_targets, uint32_t n, uint8_t* results,
+                             hipStream_t s) {
+  if (n == 0 || n_targets == 0 || !job || !records || !headers || !digests || !targets || !results)
+    return hipErrorInvalidValue;
+  if (!aligned16(job, records, headers, digests, targets, results)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(otd_share_pack, dim3((n + 255u) / 256u), dim3(256), 0, s,
+                     static_cast<const ShareJobBlock*>(job), reinterpret_cast<const uint4*>(records),
+                     reinterpret_cast<const uint4*>(headers), reinterpret_cast<const uint4*>(digests),
+                     reinterpret_cast<const uint4*>(targets), n_targets, n, reinterpret_cast<uint4*>(results));
+  return hipGetLastError();
 }
 
 }  // namespace otedama

@@ -52,6 +52,7 @@
 #include <unistd.h>
 
 #include "otedama/clock_bounds.h"
+#include "otedama/hip_check.h"
 #include "otedama/hitsink.h"
 #include "otedama/job.h"
 #include "otedama/launch_plan.h"
@@ -73,13 +74,6 @@ static double resident_mb() {
   std::fclose(f);
   return n == 2 ? double(res) * double(sysconf(_SC_PAGESIZE)) / (1024.0 * 1024.0) : 0;
 }
-
-#define OTD_HIP(call)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (call);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(e_) + " at " #call); \
-  } while (0)
 
 }  // namespace otedama
 
@@ -892,55 +886,6 @@ struct GpuMiner::Run {
 };
 
 void GpuMiner::loop() { Run(*this).run(); }
-
-// ------------------------------------------------------------- direct launches
-// Synchronous-free launch API for the Python ops layer (torch-owned buffers and
-// streams): pointers and the stream arrive as integers. Hits go to the legacy
-// device-memory slots after out[0]; no abort word.
-
-static HitSink ops_sink(uintptr_t out, uint32_t cap, uint32_t words) {
-  HitSink s;
-  s.out = reinterpret_cast<uint32_t*>(out);
-  s.cap = cap;
-  s.words = words;
-  return s;
-}
-
-void py_launch_sha256d(const Sha256dParams& p, uint32_t base, uint64_t count, uintptr_t out, uint32_t cap, int grid,
-                       uintptr_t stream) {
-  OTD_HIP(launch_sha256d_search(p, base, count, ops_sink(out, cap, 1), grid, reinterpret_cast<hipStream_t>(stream)));
-}
-
-void py_launch_sha256d_k(const Sha256dParamsK& p, uint32_t base, uint64_t count, uintptr_t out, uint32_t cap, int grid,
-                         uintptr_t stream) {
-  OTD_HIP(launch_sha256d_search_k(p, base, count, ops_sink(out, cap, 2), grid, reinterpret_cast<hipStream_t>(stream)));
-}
-
-void py_launch_sha256d_v(const Sha256dParamsV& p, uintptr_t vars, uint32_t base, uint64_t count, uintptr_t out,
-                         uint32_t cap, int grid, uintptr_t stream, int block, int chains) {
-  OTD_HIP(launch_sha256d_search_v(p, reinterpret_cast<const Sha256dVariant*>(vars), base, count,
-                                  ops_sink(out, cap, 2), grid, reinterpret_cast<hipStream_t>(stream), block, chains));
-}
-
-void py_launch_scrypt(const ScryptParams& p, uint32_t base, uint32_t count, uintptr_t xbuf, uintptr_t scratch, int gap,
-                      uintptr_t out, uint32_t cap, int grid, uintptr_t stream) {
-  OTD_HIP(launch_scrypt_search(p, base, count, reinterpret_cast<void*>(xbuf), reinterpret_cast<void*>(scratch), gap,
-                               ops_sink(out, cap, 1), grid, reinterpret_cast<hipStream_t>(stream)));
-}
-
-void py_launch_x11_stage(const X11Params& p, int stage, uint32_t base, uintptr_t H, uint32_t stride, uint32_t n,
-                         uintptr_t out, uint32_t cap, uintptr_t stream) {
-  const HitSink s = ops_sink(out, cap, 1);
-  OTD_HIP(x11_launch_stage(stage, p, base, reinterpret_cast<uint64_t*>(H), stride, n, out ? &s : nullptr,
-                           reinterpret_cast<hipStream_t>(stream)));
-}
-
-void py_launch_x11(const X11Params& p, uint32_t base, uintptr_t H, uint32_t stride, uint32_t n, uintptr_t out,
-                   uint32_t cap, uintptr_t stream) {
-  const HitSink s = ops_sink(out, cap, 1);
-  OTD_HIP(x11_launch_chain(p, base, reinterpret_cast<uint64_t*>(H), stride, n, out ? &s : nullptr,
-                           reinterpret_cast<hipStream_t>(stream)));
-}
 
 int gpu_device_count() {
   int n = 0;

@@ -31,8 +31,8 @@ HIP_SOURCES = [
     "kernels/x11_stages_b.hip",
     "kernels/digest_batch.hip",
     "kernels/share_verify.hip",
-    "kernels/share_results.hip",
     "runtime/gpu_miner.hip",
+    "runtime/ops_launch.hip",
 ]
 CXX_SOURCES = [
     "cpu/sha256_cpu.cpp",

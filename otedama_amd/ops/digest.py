@@ -17,13 +17,13 @@ from typing import Sequence
 import torch
 
 from otedama_amd.models import algorithms
+from otedama_amd.ops._args import ALIGN, byte_rows, launch_stream  # noqa: F401  (ALIGN: for importers of this module)
 from otedama_amd.ops.native import require_native
 from otedama_amd.ops.search import default_grid
 from otedama_amd.ops.tuning import SCRYPT_BLOCKS_PER_CU
 
 HEADER_BYTES = 80
 DIGEST_BYTES = 32
-ALIGN = 16  # the kernels read headers and write digests as 16-byte vectors
 
 X11_CAPACITY = 1 << 20  # headers per chain pass: 64 MiB of stage planes
 
@@ -69,24 +69,11 @@ class HeaderDigest:
             self.capacity = int(capacity) if capacity else None
 
     def _check(self, headers: torch.Tensor, out: torch.Tensor | None) -> int:
-        if not isinstance(headers, torch.Tensor) or headers.dtype != torch.uint8:
-            raise ValueError("headers must be a uint8 tensor")
-        if headers.dim() != 2 or headers.shape[1] != HEADER_BYTES:
-            raise ValueError(f"headers must have shape [n, {HEADER_BYTES}]")
-        if headers.device != self.device:
-            raise ValueError(f"headers must live on {self.device}")
-        if not headers.is_contiguous():
-            raise ValueError("headers must be contiguous")
-        n = headers.shape[0]
-        if n and headers.data_ptr() % ALIGN:
-            raise ValueError(f"headers must start at a {ALIGN}-byte aligned address")
+        n = byte_rows("headers", headers, HEADER_BYTES, self.device)
         if n >= 1 << 32:
             raise ValueError("at most 2^32 - 1 headers per launch")
         if out is not None:
-            if out.dtype != torch.uint8 or tuple(out.shape) != (n, DIGEST_BYTES) or out.device != self.device:
-                raise ValueError(f"out must be a uint8 [n, {DIGEST_BYTES}] tensor on {self.device}")
-            if not out.is_contiguous() or (n and out.data_ptr() % ALIGN):
-                raise ValueError(f"out must be contiguous and start at a {ALIGN}-byte aligned address")
+            byte_rows("out", out, DIGEST_BYTES, self.device, rows=n)
         return n
 
     def launch(self, headers: torch.Tensor, out: torch.Tensor | None = None,
@@ -95,11 +82,7 @@ class HeaderDigest:
         (default: the current stream) and return the uint8 ``[n, 32]`` result (``out`` if given) without
         synchronising. A bad argument raises ``ValueError`` before anything is enqueued."""
         n = self._check(headers, out)
-        cur = torch.cuda.current_stream(self.device)
-        if stream is None:
-            stream = cur
-        elif stream != cur:
-            stream.wait_stream(cur)  # the caller produced `headers` on the current stream
+        stream = launch_stream(self.device, stream)
         if out is None:
             with torch.cuda.stream(stream):
                 out = torch.empty((n, DIGEST_BYTES), dtype=torch.uint8, device=self.device)

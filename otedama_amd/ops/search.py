@@ -19,6 +19,7 @@ from dataclasses import dataclass
 
 import torch
 
+from otedama_amd.ops._args import launch_stream
 from otedama_amd.ops.native import require_native
 
 from otedama_amd.ops.tuning import (  # noqa: F401  (re-exported: launch geometry lives in the torch-free module)
@@ -188,11 +189,7 @@ class Sha256dSearchV:
             raise ValueError("variant table must live on the search device")
         if prep.vars.numel() != prep.n * 72 or len(prep.params) != self.native.SHA256D_V_PARAMS_SIZE:
             raise ValueError("prepared table does not match its parameter block")
-        cur = torch.cuda.current_stream(self.device)
-        if stream is None:
-            stream = cur
-        elif stream != cur:
-            stream.wait_stream(cur)  # prepare() uploaded the variant table on the current stream
+        stream = launch_stream(self.device, stream)  # prepare() uploaded the variant table on the current stream
         with torch.cuda.stream(stream):
             out[:1].zero_()
         self.launch_into(prep, base, count, out, stream)

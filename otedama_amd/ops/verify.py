@@ -10,7 +10,7 @@ the digest ops (:mod:`otedama_amd.ops.digest`):
   3. ``otd_share_verdict``  the 256-bit little-endian compare against per-share targets and the network target
 
 For a pool's live micro-batches, :meth:`ShareVerify.launch_results` ends the same chain with ``otd_share_pack``
-(csrc/kernels/share_results.hip) instead: one packed 128-byte record per share (header, hash, verdict), so that
+(the same file) instead: one packed 128-byte record per share (header, hash, verdict), so that
 :meth:`ShareVerify.results` moves one pinned buffer in and one out.
 
 Layouts of the job block, the share record and the result record: csrc/include/otedama/share_job.h. The record
@@ -23,7 +23,8 @@ from typing import Sequence
 
 import torch
 
-from otedama_amd.ops.digest import ALIGN, DIGEST_BYTES, HEADER_BYTES, HeaderDigest
+from otedama_amd.ops._args import ALIGN, byte_rows, launch_stream
+from otedama_amd.ops.digest import DIGEST_BYTES, HEADER_BYTES, HeaderDigest
 from otedama_amd.ops.share_records import (MAX_EXTRANONCE, RECORD_BYTES, RESULT_BYTES, VERDICT_BAD_INDEX,  # noqa: F401
                                            VERDICT_NETWORK, VERDICT_SHARE, pack_records, unpack_records,
                                            unpack_results)
@@ -75,22 +76,40 @@ class ShareVerify:
         if (job.dev.dtype != torch.uint8 or job.dev.numel() != self.native.SHARE_JOB_BLOCK_SIZE
                 or not job.dev.is_contiguous() or job.dev.data_ptr() % ALIGN):
             raise ValueError("job block has the wrong size or alignment")
-        for name, t, width in (("records", records, RECORD_BYTES), ("targets", targets, TARGET_BYTES)):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
-                raise ValueError(f"{name} must be a uint8 tensor")
-            if t.dim() != 2 or t.shape[1] != width:
-                raise ValueError(f"{name} must have shape [n, {width}]")
-            if t.device != self.device:
-                raise ValueError(f"{name} must live on {self.device}")
-            if not t.is_contiguous():
-                raise ValueError(f"{name} must be contiguous")
-            if t.shape[0] and t.data_ptr() % ALIGN:
-                raise ValueError(f"{name} must start at a {ALIGN}-byte aligned address")
-        if targets.shape[0] < 1:
+        n = byte_rows("records", records, RECORD_BYTES, self.device)
+        if byte_rows("targets", targets, TARGET_BYTES, self.device) < 1:
             raise ValueError("the target table is empty")
-        if records.shape[0] >= 1 << 32 or targets.shape[0] >= 1 << 32:
+        if n >= 1 << 32 or targets.shape[0] >= 1 << 32:
             raise ValueError("at most 2^32 - 1 records and targets per launch")
-        return records.shape[0]
+        return n
+
+    def _grow_rows(self, name: str, n: int, width: int, stream: torch.cuda.Stream) -> torch.Tensor:
+        """The first ``n`` rows of the op's ``[rows, width]`` buffer ``name``, reallocated on ``stream`` when it is
+        too small. The old buffer's memory stays reserved until the previous launch's stream is through with it."""
+        buf = getattr(self, name)
+        if buf is None or buf.shape[0] < n:
+            if buf is not None and self._last_stream is not None:
+                buf.record_stream(self._last_stream)
+            with torch.cuda.stream(stream):
+                buf = torch.empty((n, width), dtype=torch.uint8, device=self.device)
+            setattr(self, name, buf)
+        return buf[:n]
+
+    def _chain(self, job: PreparedJob, records: torch.Tensor, n: int, stream: torch.cuda.Stream,
+               digests: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+        """Enqueue ``otd_share_headers`` and the digest launches for ``n >= 1`` records on ``stream``, after whatever
+        the previous launch still does with the op's buffers, and return ``(headers, digests)``: views of the op's
+        buffers, the digests in the caller's tensor if it brings one."""
+        if self._last_stream is not None and self._last_stream != stream:
+            stream.wait_stream(self._last_stream)  # headers and digests are still in use by the previous launch
+        headers = self._grow_rows("headers", n, HEADER_BYTES, stream)
+        if digests is None:
+            digests = self._grow_rows("_digests", n, DIGEST_BYTES, stream)
+        self._last_stream = stream
+        self.native.launch_share_headers(job.dev.data_ptr(), records.data_ptr(), n, headers.data_ptr(),
+                                         stream.cuda_stream)
+        self.digest.launch(headers, out=digests, stream=stream)
+        return headers, digests
 
     def launch(self, job: PreparedJob, records: torch.Tensor, targets: torch.Tensor,
                stream: torch.cuda.Stream | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -100,30 +119,16 @@ class ShareVerify:
         [n, 32], headers uint8 [n, 80])`` without synchronising. ``headers`` is a view of the op's own buffer and is
         overwritten by the next launch. A bad argument raises ``ValueError`` before anything is enqueued."""
         n = self._check(job, records, targets)
-        cur = torch.cuda.current_stream(self.device)
-        if stream is None:
-            stream = cur
-        elif stream != cur:
-            stream.wait_stream(cur)  # the caller produced `records` and `targets` on the current stream
+        stream = launch_stream(self.device, stream)  # the caller produced `records` and `targets` on the current one
         with torch.cuda.stream(stream):
             verdicts = torch.empty(n, dtype=torch.uint8, device=self.device)
             digests = torch.empty((n, DIGEST_BYTES), dtype=torch.uint8, device=self.device)
         if n == 0:
             return verdicts, digests, torch.empty((0, HEADER_BYTES), dtype=torch.uint8, device=self.device)
-        if self._last_stream is not None and self._last_stream != stream:
-            stream.wait_stream(self._last_stream)  # the headers buffer is still in use by the previous launch
-        if self.headers is None or self.headers.shape[0] < n:
-            if self.headers is not None and self._last_stream is not None:
-                self.headers.record_stream(self._last_stream)
-            with torch.cuda.stream(stream):
-                self.headers = torch.empty((n, HEADER_BYTES), dtype=torch.uint8, device=self.device)
-        self._last_stream = stream
-        headers = self.headers[:n]
-        s = stream.cuda_stream
-        self.native.launch_share_headers(job.dev.data_ptr(), records.data_ptr(), n, headers.data_ptr(), s)
-        self.digest.launch(headers, out=digests, stream=stream)
+        headers, _ = self._chain(job, records, n, stream, digests)
         self.native.launch_share_verdict(job.dev.data_ptr(), records.data_ptr(), digests.data_ptr(),
-                                         targets.data_ptr(), targets.shape[0], n, verdicts.data_ptr(), s)
+                                         targets.data_ptr(), targets.shape[0], n, verdicts.data_ptr(),
+                                         stream.cuda_stream)
         return verdicts, digests, headers
 
     def launch_results(self, job: PreparedJob, records: torch.Tensor, targets: torch.Tensor,
@@ -131,45 +136,20 @@ class ShareVerify:
         """The live form of :meth:`launch`: the same arguments, checks and stream handling, one packed 128-byte
         result record per share (header 80 | hash 32 | verdict 1 | zeros 15; ``ShareResult`` in share_job.h) as
         uint8 ``[n, 128]`` (``out`` if given: that shape, contiguous, 16-byte aligned, on the op's device), without
-        synchronising: ``otd_share_headers``, the digest launches of the algorithm, then ``otd_share_pack``
-        (csrc/kernels/share_results.hip), which compares and packs. An empty batch returns an empty tensor and
-        enqueues nothing."""
+        synchronising: ``otd_share_headers``, the digest launches of the algorithm, then ``otd_share_pack``, which
+        compares and packs. An empty batch returns an empty tensor and enqueues nothing."""
         n = self._check(job, records, targets)
         if out is not None:
-            if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, RESULT_BYTES)
-                    or out.device != self.device):
-                raise ValueError(f"out must be a uint8 [n, {RESULT_BYTES}] tensor on {self.device}")
-            if not out.is_contiguous() or (n and out.data_ptr() % ALIGN):
-                raise ValueError(f"out must be contiguous and start at a {ALIGN}-byte aligned address")
+            byte_rows("out", out, RESULT_BYTES, self.device, rows=n)
         if n == 0:
             return out if out is not None else torch.empty((0, RESULT_BYTES), dtype=torch.uint8, device=self.device)
-        cur = torch.cuda.current_stream(self.device)
-        if stream is None:
-            stream = cur
-        elif stream != cur:
-            stream.wait_stream(cur)  # the caller produced `records` and `targets` on the current stream
+        stream = launch_stream(self.device, stream)
         if out is None:
             with torch.cuda.stream(stream):
                 out = torch.empty((n, RESULT_BYTES), dtype=torch.uint8, device=self.device)
-        s = stream.cuda_stream
-        if self._last_stream is not None and self._last_stream != stream:
-            stream.wait_stream(self._last_stream)  # headers and digests are still in use by the previous launch
-        if self.headers is None or self.headers.shape[0] < n:
-            if self.headers is not None and self._last_stream is not None:
-                self.headers.record_stream(self._last_stream)
-            with torch.cuda.stream(stream):
-                self.headers = torch.empty((n, HEADER_BYTES), dtype=torch.uint8, device=self.device)
-        if self._digests is None or self._digests.shape[0] < n:
-            if self._digests is not None and self._last_stream is not None:
-                self._digests.record_stream(self._last_stream)
-            with torch.cuda.stream(stream):
-                self._digests = torch.empty((n, DIGEST_BYTES), dtype=torch.uint8, device=self.device)
-        self._last_stream = stream
-        headers, digests = self.headers[:n], self._digests[:n]
-        self.native.launch_share_headers(job.dev.data_ptr(), records.data_ptr(), n, headers.data_ptr(), s)
-        self.digest.launch(headers, out=digests, stream=stream)
+        headers, digests = self._chain(job, records, n, stream)
         self.native.launch_share_pack(job.dev.data_ptr(), records.data_ptr(), headers.data_ptr(), digests.data_ptr(),
-                                      targets.data_ptr(), targets.shape[0], n, out.data_ptr(), s)
+                                      targets.data_ptr(), targets.shape[0], n, out.data_ptr(), stream.cuda_stream)
         return out
 
     def _grown(self, name: str, nbytes: int, pinned: bool) -> torch.Tensor:
@@ -181,6 +161,18 @@ class ShareVerify:
             setattr(self, name, buf)
         return buf
 
+    @staticmethod
+    def _packed(job: PreparedJob, shares: Sequence[tuple], targets: Sequence[bytes],
+                target_indices: Sequence[int] | None) -> tuple[bytes, bytes, int]:
+        """The host side of both synchronous entries: ``(records, target table, number of targets)`` as bytes, with
+        ``target_indices`` defaulting to target 0 for every share."""
+        targets = [bytes(t) for t in targets]
+        if not targets or any(len(t) != TARGET_BYTES for t in targets):
+            raise ValueError(f"need at least one target, each {TARGET_BYTES} bytes")
+        if target_indices is None:
+            target_indices = [0] * len(shares)
+        return pack_records(shares, target_indices, job.en_size), b"".join(targets), len(targets)
+
     def results(self, job: PreparedJob, shares: Sequence[tuple], targets: Sequence[bytes],
                 target_indices: Sequence[int] | None = None) -> list[tuple[bytes, bytes, int]]:
         """The live entry: ``(extranonce, ntime, nonce, version)`` tuples and 32-byte targets in, ``(header, hash,
@@ -188,27 +180,22 @@ class ShareVerify:
         targets) goes to the device and one pinned buffer of result records comes back, both copies non-blocking on
         the current stream around :meth:`launch_results`, then one stream synchronise. The four buffers are the op's
         own and grow to the largest batch seen; the call is not re-entrant."""
-        targets = [bytes(t) for t in targets]
-        if not targets or any(len(t) != TARGET_BYTES for t in targets):
-            raise ValueError(f"need at least one target, each {TARGET_BYTES} bytes")
-        if target_indices is None:
-            target_indices = [0] * len(shares)
-        packed = pack_records(shares, target_indices, job.en_size)
+        packed, table, n_targets = self._packed(job, shares, targets, target_indices)
         n = len(shares)
         if n == 0:
             return []
         rec_bytes, out_bytes = n * RECORD_BYTES, n * RESULT_BYTES
-        in_bytes = rec_bytes + len(targets) * TARGET_BYTES
+        in_bytes = rec_bytes + n_targets * TARGET_BYTES
         pin_in, dev_in = self._grown("_pin_in", in_bytes, True), self._grown("_dev_in", in_bytes, False)
         pin_out, dev_out = self._grown("_pin_out", out_bytes, True), self._grown("_dev_out", out_bytes, False)
         host = memoryview(pin_in.numpy())
         host[:rec_bytes] = packed
-        host[rec_bytes:in_bytes] = b"".join(targets)
+        host[rec_bytes:in_bytes] = table
         stream = torch.cuda.current_stream(self.device)
         dev_in[:in_bytes].copy_(pin_in[:in_bytes], non_blocking=True)
         out = dev_out[:out_bytes].view(n, RESULT_BYTES)
         self.launch_results(job, dev_in[:rec_bytes].view(n, RECORD_BYTES),
-                            dev_in[rec_bytes:in_bytes].view(len(targets), TARGET_BYTES), out=out)
+                            dev_in[rec_bytes:in_bytes].view(n_targets, TARGET_BYTES), out=out)
         pin_out[:out_bytes].copy_(dev_out[:out_bytes], non_blocking=True)
         stream.synchronize()
         return unpack_results(memoryview(pin_out.numpy())[:out_bytes])
@@ -218,16 +205,11 @@ class ShareVerify:
         """Synchronous convenience: ``(extranonce, ntime, nonce, version)`` tuples and 32-byte targets in, the lists
         ``(verdict bytes, 32-byte hashes, 80-byte headers)`` out. ``target_indices`` defaults to target 0 for every
         share."""
-        targets = [bytes(t) for t in targets]
-        if not targets or any(len(t) != TARGET_BYTES for t in targets):
-            raise ValueError(f"need at least one target, each {TARGET_BYTES} bytes")
-        if target_indices is None:
-            target_indices = [0] * len(shares)
-        packed = pack_records(shares, target_indices, job.en_size)
+        packed, table, n_targets = self._packed(job, shares, targets, target_indices)
         if not shares:
             return [], [], []
         recs = torch.frombuffer(bytearray(packed), dtype=torch.uint8).view(len(shares), RECORD_BYTES)
-        tgts = torch.frombuffer(bytearray(b"".join(targets)), dtype=torch.uint8).view(len(targets), TARGET_BYTES)
+        tgts = torch.frombuffer(bytearray(table), dtype=torch.uint8).view(n_targets, TARGET_BYTES)
         v, d, h = self.launch(job, recs.to(self.device), tgts.to(self.device))
         torch.cuda.current_stream(self.device).synchronize()
         vb, db, hb = (t.cpu().numpy().tobytes() for t in (v, d, h))

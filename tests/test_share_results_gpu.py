@@ -1,5 +1,5 @@
 """Live share verification on a real MI355X: ``ShareVerify.launch_results`` / ``results`` (otedama_amd/ops/verify.py;
-``otd_share_headers``, the digest launches and ``otd_share_pack`` of csrc/kernels/share_results.hip, for every
+``otd_share_headers``, the digest launches and ``otd_share_pack`` of csrc/kernels/share_verify.hip, for every
 algorithm) and the pool's micro-batcher on the GPU.
 
 Every comparison is exact byte equality against the Python oracle ``check_shares(device=None)``; the target tables
@@ -255,6 +255,54 @@ def test_launch_results_on_a_side_stream_matches():
         # and back on the current stream: the op waits for its previous launch's stream
         assert _launch_results(op, job, shares[:65], targets, indices[:65]) == ref
     assert _launch_results(_op(), job, shares[:65], targets, indices[:65]) == want[:65]
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(algorithm: str):
+    from otedama_amd.pool.batch import check_shares
+
+    job, shares, targets, indices, want = _sized_case(7)
+    return want if algorithm == "sha256d" else check_shares(algorithm, job, shares, targets, indices)
+
+
+@pytest.mark.parametrize("algorithm,kw", [("sha256d", {}), ("x11", {"capacity": 256})])
+def test_launch_and_launch_results_interleaved_on_one_op(algorithm, kw):
+    """Both entries share the op's headers buffer and ``_last_stream``: alternate them across two streams on a fresh
+    op, with a batch that outgrows the buffer while the side stream's launch was the last to use it."""
+    import torch
+
+    from otedama_amd.ops.verify import ShareVerify, pack_records
+
+    job, shares, targets, indices, _ = _sized_case(7)
+    want = _oracle(algorithm)
+    op = ShareVerify(algorithm, DEV, **kw)
+    prep = _prepare(op, job)
+    tgts = _dev(b"".join(targets), 32)
+    side = torch.cuda.Stream(DEV)
+    cur = torch.cuda.current_stream(DEV)
+
+    def packed(n):
+        return _dev(pack_records(shares[:n], indices[:n], job.en_size), 32)
+
+    def launch_results(n, stream):
+        r = op.launch_results(prep, packed(n), tgts, stream=stream)
+        (stream or cur).synchronize()
+        assert _records(r.cpu().numpy().tobytes()) == want[:n], n
+
+    def launch(n, stream):
+        v, d, h = op.launch(prep, packed(n), tgts, stream=stream)
+        (stream or cur).synchronize()
+        assert h.data_ptr() == op.headers.data_ptr() and h.shape == (n, 80)
+        vb, db, hb = (t.cpu().numpy().tobytes() for t in (v, d, h))
+        assert [(hb[80 * i:80 * i + 80], db[32 * i:32 * i + 32], vb[i]) for i in range(n)] == want[:n], n
+
+    launch_results(65, side)
+    assert op.headers.shape[0] == 65 and op._last_stream == side
+    launch(257, None)  # the headers buffer grows while the side stream's launch was its last user
+    assert op.headers.shape[0] == 257 and op._last_stream == cur
+    launch_results(1, None)
+    launch(64, side)
+    assert op.headers.shape[0] == 257 and op._last_stream == side
 
 
 @pytest.mark.parametrize("min_gpu,gpu_shares", [(1, 11), (64, 0)])
