@@ -585,6 +585,27 @@ PYBIND11_MODULE(_native, m) {
   }, py::arg("job"), py::arg("records"), py::arg("headers"), py::arg("digests"), py::arg("targets"),
      py::arg("n_targets"), py::arg("n"), py::arg("results"), py::arg("stream") = 0);
 
+  // Channel roots: n 16-byte extranonce prefixes against one job block -> n 32-byte merkle roots.
+  m.def("share_roots_cpu", [](const py::bytes& job_block, const py::bytes& prefixes) {
+    std::string js = need(job_block, sizeof(ShareJobBlock), "job_block"), ps = prefixes;
+    if (ps.size() % 16) throw std::invalid_argument("prefixes: expected a multiple of 16 bytes");
+    ShareJobBlock job;
+    std::memcpy(&job, js.data(), sizeof job);
+    std::string out(ps.size() * 2, '\0');
+    {
+      py::gil_scoped_release r;  // a pool's fan-out may be tens of thousands of prefixes
+      share_roots_cpu(job, reinterpret_cast<const uint8_t*>(ps.data()), ps.size() / 16,
+                      reinterpret_cast<uint8_t*>(&out[0]));
+    }
+    return py::bytes(out);
+  }, py::arg("job_block"), py::arg("prefixes"));
+  m.def("launch_channel_roots", [](uintptr_t job, uintptr_t prefixes, uint32_t n, uintptr_t roots, uintptr_t stream) {
+    if (job == 0 || prefixes == 0 || roots == 0 || n == 0)
+      throw std::invalid_argument("need job, prefixes, roots != 0, n > 0");
+    if ((job | prefixes | roots) & 15u) throw std::invalid_argument("job, prefixes and roots must be 16-byte aligned");
+    py_launch_channel_roots(job, prefixes, n, roots, stream);
+  }, py::arg("job"), py::arg("prefixes"), py::arg("n"), py::arg("roots"), py::arg("stream") = 0);
+
   py::class_<MinerBase, std::shared_ptr<MinerBase>>(m, "Miner")
       .def("start", &MinerBase::start, py::call_guard<py::gil_scoped_release>())
       .def("stop", &MinerBase::stop, py::call_guard<py::gil_scoped_release>())

@@ -1,7 +1,7 @@
 // Host side of share verification (otedama/share_job.h): the job block builder and a plain C++ walker of the same
 // block, so that the block format (every len(coinb1) mod 64, every extranonce alignment, every padding edge) is
 // testable without a GPU. otd_share_headers (csrc/kernels/share_verify.hip) does per lane what the walker does per
-// record.
+// record, otd_channel_roots (csrc/kernels/channel_roots.hip) what share_roots_cpu does per prefix.
 #include "otedama/share_job.h"
 
 #include <cstring>
@@ -96,39 +96,48 @@ ShareJobBlock share_job_prepare(const std::string& coinb1, const std::string& co
   return job;
 }
 
+namespace {
+
+// The merkle root of one extranonce against a checked block, as big-endian state words: the coinbase txid (midstate,
+// the tail blocks with the extranonce patched in, then the hash of that digest) folded over the branches.
+void root_words(const ShareJobBlock& job, const uint8_t* extranonce, uint32_t cur[8]) {
+  uint32_t st[8];
+  std::memcpy(st, job.midstate, 32);
+  for (uint32_t b = 0; b < job.tail_blocks; ++b) {
+    uint8_t blk[64];
+    for (int w = 0; w < 16; ++w) store_be32(blk + 4 * w, job.tail[16 * b + uint32_t(w)]);
+    for (uint32_t j = 0; j < job.en_size; ++j) {
+      const uint32_t at = job.en_offset + j;
+      if (at / 64 == b) blk[at % 64] = extranonce[j];
+    }
+    sha256_compress(st, blk);
+  }
+  sha256_of_digest(st, cur);
+  // merkle fold: cur = sha256d(cur | branch)
+  for (uint32_t b = 0; b < job.n_branches; ++b) {
+    uint8_t blk[64];
+    for (int k = 0; k < 8; ++k) {
+      store_be32(blk + 4 * k, cur[k]);
+      store_be32(blk + 32 + 4 * k, job.branches[8 * b + uint32_t(k)]);
+    }
+    std::memcpy(st, kSha256IV, 32);
+    sha256_compress(st, blk);
+    uint8_t pad[64] = {0};
+    pad[0] = 0x80;
+    pad[62] = 0x02;  // 512 bits
+    sha256_compress(st, pad);
+    sha256_of_digest(st, cur);
+  }
+}
+
+}  // namespace
+
 void share_headers_cpu(const ShareJobBlock& job, const ShareRec* recs, size_t n, uint8_t* out) {
   check_block(job);
   for (size_t i = 0; i < n; ++i) {
     const ShareRec& r = recs[i];
-    // coinbase txid: midstate, the tail blocks with this share's extranonce, then the hash of that digest
-    uint32_t st[8];
-    std::memcpy(st, job.midstate, 32);
-    for (uint32_t b = 0; b < job.tail_blocks; ++b) {
-      uint8_t blk[64];
-      for (int w = 0; w < 16; ++w) store_be32(blk + 4 * w, job.tail[16 * b + uint32_t(w)]);
-      for (uint32_t j = 0; j < job.en_size; ++j) {
-        const uint32_t at = job.en_offset + j;
-        if (at / 64 == b) blk[at % 64] = r.extranonce[j];
-      }
-      sha256_compress(st, blk);
-    }
     uint32_t cur[8];
-    sha256_of_digest(st, cur);
-    // merkle fold: cur = sha256d(cur | branch)
-    for (uint32_t b = 0; b < job.n_branches; ++b) {
-      uint8_t blk[64];
-      for (int k = 0; k < 8; ++k) {
-        store_be32(blk + 4 * k, cur[k]);
-        store_be32(blk + 32 + 4 * k, job.branches[8 * b + uint32_t(k)]);
-      }
-      std::memcpy(st, kSha256IV, 32);
-      sha256_compress(st, blk);
-      uint8_t pad[64] = {0};
-      pad[0] = 0x80;
-      pad[62] = 0x02;  // 512 bits
-      sha256_compress(st, pad);
-      sha256_of_digest(st, cur);
-    }
+    root_words(job, r.extranonce, cur);
     uint8_t* h = out + 80 * i;
     store_le32(h, r.version);
     for (int k = 0; k < 8; ++k) store_le32(h + 4 + 4 * k, job.prev_hash[k]);
@@ -136,6 +145,15 @@ void share_headers_cpu(const ShareJobBlock& job, const ShareRec* recs, size_t n,
     store_le32(h + 68, r.ntime);
     store_le32(h + 72, job.nbits);
     store_le32(h + 76, r.nonce);
+  }
+}
+
+void share_roots_cpu(const ShareJobBlock& job, const uint8_t* prefixes, size_t n, uint8_t* out) {
+  check_block(job);
+  for (size_t i = 0; i < n; ++i) {
+    uint32_t cur[8];
+    root_words(job, prefixes + 16 * i, cur);
+    for (int k = 0; k < 8; ++k) store_be32(out + 32 * i + 4 * k, cur[k]);
   }
 }
 

@@ -55,6 +55,11 @@ void py_launch_share_verdict(uintptr_t job, uintptr_t records, uintptr_t digests
 void py_launch_share_pack(uintptr_t job, uintptr_t records, uintptr_t headers, uintptr_t digests, uintptr_t targets,
                           uint32_t n_targets, uint32_t n, uintptr_t results, uintptr_t stream);
 
+// Channel roots (otd_channel_roots of channel_roots.hip): n 16-byte extranonce prefixes (the job's first en_size bytes
+// of each are used) against one uploaded job block -> n 32-byte merkle roots at roots + 32 * i, in header byte order.
+// Same conventions as above; every array is 16-byte aligned.
+void py_launch_channel_roots(uintptr_t job, uintptr_t prefixes, uint32_t n, uintptr_t roots, uintptr_t stream);
+
 }  // namespace otedama
 
 #ifdef __HIPCC__
@@ -98,6 +103,9 @@ hipError_t launch_share_verdict(const void* job, const uint8_t* records, const u
 // The same conventions; here every array, the results included, is 16-byte aligned.
 hipError_t launch_share_pack(const void* job, const uint8_t* records, const uint8_t* headers, const uint8_t* digests,
                              const uint8_t* targets, uint32_t n_targets, uint32_t n, uint8_t* results, hipStream_t s);
+// Channel roots: hipErrorInvalidValue, before launching anything, for n == 0, a null pointer or an array (the job
+// block included) that is not 16-byte aligned.
+hipError_t launch_channel_roots(const void* job, const uint8_t* prefixes, uint32_t n, uint8_t* roots, hipStream_t s);
 
 }  // namespace otedama
 #endif

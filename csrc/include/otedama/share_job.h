@@ -81,4 +81,10 @@ void share_headers_cpu(const ShareJobBlock& job, const ShareRec* recs, size_t n,
 void share_results_cpu(const ShareJobBlock& job, const ShareRec* recs, size_t n, const uint8_t* targets,
                        size_t n_targets, ShareResult* out);
 
+// The merkle roots of n extranonce prefixes against one job (what otd_channel_roots of
+// csrc/kernels/channel_roots.hip writes): prefixes + 16 * i holds prefix i, of which the first en_size bytes are used;
+// out + 32 * i receives sha256d(coinb1 | prefix | coinb2) folded over the job's branches, in header byte order.
+// Throws std::invalid_argument like share_headers_cpu.
+void share_roots_cpu(const ShareJobBlock& job, const uint8_t* prefixes, size_t n, uint8_t* out);
+
 }  // namespace otedama

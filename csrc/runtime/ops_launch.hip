@@ -107,4 +107,10 @@ void py_launch_share_pack(uintptr_t job, uintptr_t records, uintptr_t headers, u
             "launch_share_pack");
 }
 
+void py_launch_channel_roots(uintptr_t job, uintptr_t prefixes, uint32_t n, uintptr_t roots, uintptr_t stream) {
+  hip_check(launch_channel_roots(reinterpret_cast<const void*>(job), reinterpret_cast<const uint8_t*>(prefixes), n,
+                                 reinterpret_cast<uint8_t*>(roots), reinterpret_cast<hipStream_t>(stream)),
+            "launch_channel_roots");
+}
+
 }  // namespace otedama

@@ -31,6 +31,7 @@ HIP_SOURCES = [
     "kernels/x11_stages_b.hip",
     "kernels/digest_batch.hip",
     "kernels/share_verify.hip",
+    "kernels/channel_roots.hip",
     "runtime/gpu_miner.hip",
     "runtime/ops_launch.hip",
 ]

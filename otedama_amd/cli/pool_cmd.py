@@ -38,7 +38,7 @@ def apply_config_file(fs: FlagSet, stderr: TextIO) -> None:
              ("retarget-seconds", ps.vardiff_retarget_seconds), ("journal", ps.journal_path),
              ("verify-device", ps.verify_device), ("verify-batch-ms", ps.verify_batch_ms),
              ("verify-batch-max", ps.verify_batch_max), ("verify-min-gpu", ps.verify_min_gpu),
-             ("http-addr", cfg.http_addr))
+             ("job-device", ps.job_device), ("job-min-gpu", ps.job_min_gpu), ("http-addr", cfg.http_addr))
     default = type(ps)()
     for flag, value in pairs:
         unset_in_file = flag != "http-addr" and value == getattr(default, _FILE_FIELD[flag])
@@ -52,7 +52,8 @@ _FILE_FIELD = {"algorithms": "algorithm", "listen-sv2": "listen_sv2", "listen-v1
                "difficulty": "initial_difficulty", "share-seconds": "target_share_seconds",
                "retarget-seconds": "vardiff_retarget_seconds", "journal": "journal_path",
                "verify-device": "verify_device", "verify-batch-ms": "verify_batch_ms",
-               "verify-batch-max": "verify_batch_max", "verify-min-gpu": "verify_min_gpu"}
+               "verify-batch-max": "verify_batch_max", "verify-min-gpu": "verify_min_gpu",
+               "job-device": "job_device", "job-min-gpu": "job_min_gpu"}
 
 
 def verify_options(fs: FlagSet) -> dict:
@@ -70,6 +71,21 @@ def verify_options_error(opts: dict) -> str | None:
         return "--verify-batch-ms and --verify-batch-max must be positive"
     if opts["verify_min_gpu"] < 0:
         return "--verify-min-gpu must not be negative (0 = the algorithm's measured default)"
+    return None
+
+
+def job_options(fs: FlagSet) -> dict:
+    """The job fan-out's PoolOptions fields from the (file-filled) flags."""
+    return {"job_device": fs["job-device"], "job_min_gpu": fs["job-min-gpu"]}
+
+
+def job_options_error(opts: dict) -> str | None:
+    from otedama_amd.pool.microbatch import valid_device
+
+    if not valid_device(opts["job_device"]):
+        return f"--job-device {opts['job_device']!r} must be empty (off), cpu or cuda:N"
+    if opts["job_min_gpu"] < 0:
+        return "--job-min-gpu must not be negative (0 = the measured default)"
     return None
 
 
@@ -97,6 +113,8 @@ def pool_flags(stderr: TextIO) -> FlagSet:
     fs.float("verify-batch-ms", 2.0, "Micro-batch flush delay after the oldest pending submit, in milliseconds.")
     fs.int("verify-batch-max", 4096, "Micro-batch flush size.")
     fs.int("verify-min-gpu", 0, "Batches with fewer shares are hashed on the CPU (0 = the algorithm's measured default).")
+    fs.string("job-device", "", "A job's SV2 standard-channel merkle roots in one call: cpu or cuda:N (empty = off).")
+    fs.int("job-min-gpu", 0, "Fan-outs to fewer standard channels stay on the CPU (0 = the measured default).")
     fs.string("config", "", "Path to the YAML config file (default: $OTEDAMA_CONFIG or ~/.config/otedama/config.yaml).")
     return fs
 
@@ -119,7 +137,7 @@ def cmd_pool(args: list[str], stdout: TextIO, stderr: TextIO) -> int:
         if err:
             stderr.write(f"pool: payout address invalid: {err}\n")
             return EXIT_CONFIG
-    err = verify_options_error(verify_options(fs))
+    err = verify_options_error(verify_options(fs)) or job_options_error(job_options(fs))
     if err:
         stderr.write(f"pool: {err}\n")
         return EXIT_CONFIG
@@ -162,7 +180,7 @@ async def _serve(fs, algos: list[str], stdout: TextIO) -> int:
                            journal_path=journal or ":memory:", payout_scheme=fs["payout-scheme"],
                            dialect=fs["dialect"], noise=fs["sv2-noise"], noise_suite=fs["noise-suite"],
                            coinbase_message=fs.values.get("coinbase-message", PoolOptions.coinbase_message),
-                           noise_authority_secret=int(fs["noise-authority-key"] or "0", 16), **verify_options(fs))
+                           noise_authority_secret=int(fs["noise-authority-key"] or "0", 16), **verify_options(fs), **job_options(fs))
 
         def log(level, msg):
             stdout.write(f"[{level}] {msg}\n")

@@ -99,6 +99,9 @@ class PoolServerConfig:
     verify_batch_ms: float = 2.0        # flush this long after the oldest pending submit
     verify_batch_max: int = 4096        # flush at this many pending submits
     verify_min_gpu: int = 0             # fewer survivors than this are hashed on the CPU; 0 = per-algorithm default
+    # a job's SV2 standard-channel merkle roots in one call (pool/jobroots.py); "" = off
+    job_device: str = ""                # "", "cpu" or "cuda:N"
+    job_min_gpu: int = 0                # fan-outs to fewer channels are computed on the CPU; 0 = the measured default
 
 
 @dataclass
@@ -192,6 +195,10 @@ class Config:
             issues.append("pool_server.verify_batch_max must be > 0")
         if ps.verify_min_gpu < 0:
             issues.append("pool_server.verify_min_gpu must be >= 0 (0 = the algorithm's default)")
+        if not valid_device(str(ps.job_device)):
+            issues.append(f"pool_server.job_device {ps.job_device!r} is not one of \"\", cpu, cuda:N")
+        if ps.job_min_gpu < 0:
+            issues.append("pool_server.job_min_gpu must be >= 0 (0 = the measured default)")
         if issues:
             raise ConfigError("config validation failed:\n  - " + "\n  - ".join(issues))
 

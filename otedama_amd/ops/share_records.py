@@ -1,6 +1,7 @@
 """The 32-byte share record of the share-verification op (csrc/include/otedama/share_job.h ``ShareRec``), packed
 and unpacked without torch, so the pool layer (pool/batch.py) can form a batch before it decides whether a GPU is
-involved at all. ``ops.verify`` re-exports these.
+involved at all. ``ops.verify`` re-exports these. The prefix and root rows of the channel-roots op (``ops.roots``)
+are packed here too, for the same reason.
 
     bytes 0..15   extranonce (the first ``en_size`` bytes are used, the rest are zero)
     bytes 16..19  ntime      bytes 20..23  nonce      bytes 24..27  version (full rolled version)
@@ -23,6 +24,10 @@ _REC = struct.Struct("<16sIIII")
 # verdict byte, 113..127 zero.
 RESULT_BYTES = 128
 _RES = struct.Struct("<80s32sB15x")
+
+# The channel-roots op (``ops.roots``): one 16-byte row per extranonce prefix in, one 32-byte merkle root out.
+PREFIX_BYTES = 16
+ROOT_BYTES = 32
 
 
 def pack_records(shares: Sequence[tuple], target_indices: Sequence[int], en_size: int) -> bytes:
@@ -68,3 +73,23 @@ def unpack_results(raw, n: int | None = None) -> list[tuple[bytes, bytes, int]]:
     if len(view) % RESULT_BYTES:
         raise ValueError(f"results must be a multiple of {RESULT_BYTES} bytes")
     return list(_RES.iter_unpack(view))
+
+
+def pack_prefixes(prefixes: Sequence[bytes], en_size: int) -> bytes:
+    """Prefix rows as ``otd_channel_roots`` and ``share_roots_cpu`` read them: every prefix exactly ``en_size``
+    bytes (anything else raises ``ValueError``), zero-padded to 16."""
+    if not 1 <= en_size <= MAX_EXTRANONCE:
+        raise ValueError(f"en_size must be in 1..{MAX_EXTRANONCE}")
+    pad = bytes(PREFIX_BYTES - en_size)
+    for i, p in enumerate(prefixes):
+        if len(p) != en_size:
+            raise ValueError(f"prefix {i} is {len(p)} bytes, the job takes {en_size}")
+    return b"".join(bytes(p) + pad for p in prefixes)
+
+
+def unpack_roots(raw) -> list[bytes]:
+    """Root rows (bytes, bytearray or memoryview) -> one 32-byte root per prefix."""
+    raw = bytes(raw)
+    if len(raw) % ROOT_BYTES:
+        raise ValueError(f"roots must be a multiple of {ROOT_BYTES} bytes")
+    return [raw[i:i + ROOT_BYTES] for i in range(0, len(raw), ROOT_BYTES)]

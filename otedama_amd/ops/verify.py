@@ -39,6 +39,27 @@ class PreparedJob:
     en_size: int
 
 
+def check_prepared(job, device: torch.device, block_size: int) -> None:
+    """``ValueError`` unless ``job`` is a :class:`PreparedJob` whose block lives on ``device`` as the kernels read
+    it."""
+    if not isinstance(job, PreparedJob) or not isinstance(job.dev, torch.Tensor):
+        raise ValueError("job must come from prepare()")
+    if job.dev.device != device:
+        raise ValueError(f"job was prepared for {job.dev.device}, the op runs on {device}")
+    if (job.dev.dtype != torch.uint8 or job.dev.numel() != block_size
+            or not job.dev.is_contiguous() or job.dev.data_ptr() % ALIGN):
+        raise ValueError("job block has the wrong size or alignment")
+
+
+def prepare_job(native, device: torch.device, coinb1: bytes, coinb2: bytes, en_size: int, prev_hash: bytes,
+                nbits: int, branches: Sequence[bytes]) -> PreparedJob:
+    """Build the job block and upload it to ``device``; ``ValueError`` for a job over the block's limits."""
+    block = native.share_job_prepare(bytes(coinb1), bytes(coinb2), int(en_size), bytes(prev_hash),
+                                     int(nbits) & 0xFFFFFFFF, [bytes(b) for b in branches])
+    dev = torch.frombuffer(bytearray(block), dtype=torch.uint8).to(device)
+    return PreparedJob(block, dev, int(en_size))
+
+
 class ShareVerify:
     """Reusable share verifier for one algorithm on one device. It owns a :class:`HeaderDigest` of the same
     algorithm and the headers buffer between the two; ``capacity`` and ``grid`` are the digest op's."""
@@ -63,19 +84,10 @@ class ShareVerify:
         """Build the job block (midstate, padded tail template, branches, network target) and upload it. A job over
         the block's limits (tail of more than 32 blocks, more than 32 branches, ``en_size`` outside 1..16) raises
         ``ValueError``: verify it on the CPU."""
-        block = self.native.share_job_prepare(bytes(coinb1), bytes(coinb2), int(en_size), bytes(prev_hash),
-                                              int(nbits) & 0xFFFFFFFF, [bytes(b) for b in branches])
-        dev = torch.frombuffer(bytearray(block), dtype=torch.uint8).to(self.device)
-        return PreparedJob(block, dev, int(en_size))
+        return prepare_job(self.native, self.device, coinb1, coinb2, en_size, prev_hash, nbits, branches)
 
     def _check(self, job: PreparedJob, records: torch.Tensor, targets: torch.Tensor) -> int:
-        if not isinstance(job, PreparedJob) or not isinstance(job.dev, torch.Tensor):
-            raise ValueError("job must come from prepare()")
-        if job.dev.device != self.device:
-            raise ValueError(f"job was prepared for {job.dev.device}, the op runs on {self.device}")
-        if (job.dev.dtype != torch.uint8 or job.dev.numel() != self.native.SHARE_JOB_BLOCK_SIZE
-                or not job.dev.is_contiguous() or job.dev.data_ptr() % ALIGN):
-            raise ValueError("job block has the wrong size or alignment")
+        check_prepared(job, self.device, self.native.SHARE_JOB_BLOCK_SIZE)
         n = byte_rows("records", records, RECORD_BYTES, self.device)
         if byte_rows("targets", targets, TARGET_BYTES, self.device) < 1:
             raise ValueError("the target table is empty")

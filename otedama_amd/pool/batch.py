@@ -5,6 +5,9 @@
 integer compares). With a device the whole batch is one ``ops.verify.ShareVerify.verify``: headers, hashes and
 compares happen on the GPU. Both paths return the same list. Importing this module imports neither torch nor the
 native extension.
+
+:func:`channel_roots` is the same three-way choice for a job's fan-out to Stratum V2 standard channels: one job and
+n extranonce prefixes in, n merkle roots out.
 """
 from __future__ import annotations
 
@@ -30,10 +33,15 @@ class ShareJob:
 
 
 _verify_ops: dict[tuple[str, str], object] = {}  # (algorithm, device) -> ops.verify.ShareVerify
+_roots_ops: dict[str, object] = {}  # device -> ops.roots.ChannelRoots
+
+
+def root_of(job: ShareJob, extranonce: bytes) -> bytes:
+    return merkle_root_from_branches(sha256d(job.coinb1 + extranonce + job.coinb2), job.branches)
 
 
 def header_of(job: ShareJob, extranonce: bytes, ntime: int, nonce: int, version: int) -> bytes:
-    root = merkle_root_from_branches(sha256d(job.coinb1 + extranonce + job.coinb2), job.branches)
+    root = root_of(job, extranonce)
     return (struct.pack("<I", version & 0xFFFFFFFF) + job.prev_hash + root
             + struct.pack("<III", ntime & 0xFFFFFFFF, job.nbits & 0xFFFFFFFF, nonce & 0xFFFFFFFF))
 
@@ -83,3 +91,40 @@ def check_shares(algorithm: str, job: ShareJob, shares: Sequence[tuple], targets
             verdict = (VERDICT_SHARE if hv <= tints[idx] else 0) | (VERDICT_NETWORK if hv <= network else 0)
         out.append((hdr, h, verdict))
     return out
+
+
+def channel_roots(job: ShareJob, prefixes: Sequence[bytes], device=None) -> list[bytes]:
+    """The merkle root of ``job`` for every extranonce prefix (each ``job.en_size`` bytes), in order: the bytes
+    ``PoolServer.merkle_root_for`` returns. ``device=None``: Python, one prefix at a time. ``"cpu"``: the native
+    ``share_roots_cpu``. ``"cuda:N"``: one ``ops.roots.ChannelRoots.roots`` round trip on that GPU. A job over the
+    job block's limits is computed in Python whatever the device."""
+    prefixes = [bytes(p) for p in prefixes]
+    for i, p in enumerate(prefixes):
+        if len(p) != job.en_size:
+            raise ValueError(f"prefix {i} is {len(p)} bytes, the job takes {job.en_size}")
+    if device is not None and prefixes:
+        args = (job.coinb1, job.coinb2, job.en_size, job.prev_hash, job.nbits & 0xFFFFFFFF, list(job.branches))
+        if str(device) == "cpu":
+            from otedama_amd.ops.native import require_native
+            from otedama_amd.ops.share_records import pack_prefixes, unpack_roots
+
+            native = require_native()
+            try:
+                block = native.share_job_prepare(*args)
+            except ValueError:
+                block = None  # over the block's limits: the Python path below
+            if block is not None:
+                return unpack_roots(native.share_roots_cpu(block, pack_prefixes(prefixes, job.en_size)))
+        else:
+            from otedama_amd.ops.roots import ChannelRoots  # imports torch
+
+            op = _roots_ops.get(str(device))
+            if op is None:
+                op = _roots_ops[str(device)] = ChannelRoots(device)
+            try:
+                prepared = op.prepare(*args)
+            except ValueError:
+                prepared = None  # as above
+            if prepared is not None:
+                return op.roots(prepared, prefixes)
+    return [root_of(job, p) for p in prefixes]

@@ -84,6 +84,11 @@ class PoolOptions:
     verify_batch_ms: float = 2.0   # flush this long after the oldest pending submit (the wait added to a lone share)
     verify_batch_max: int = 4096   # flush at this many pending submits (bounds the pinned staging memory)
     verify_min_gpu: int = 0        # a flush with fewer survivors is hashed on the CPU; 0 = the algorithm's default
+    # A job's fan-out to SV2 standard channels (pool/jobroots.py). "" = off: every channel's merkle root is hashed
+    # on its own in Python, as before. "cpu": all roots of a job in one native call. "cuda:N": in one launch on that
+    # GPU (ops.roots.ChannelRoots.roots).
+    job_device: str = ""
+    job_min_gpu: int = 0           # a fan-out to fewer standard channels is computed on the CPU; 0 = the default
 
 
 @dataclass
@@ -202,6 +207,12 @@ class PoolServer:
         # replaces its device path (tests inject one; None = ShareVerify.results on opts.verify_device)
         self._batcher = None
         self.verify_hasher = None
+        # the job fan-out, made by the first _make_job when opts.job_device is set; `job_roots_fn` replaces its
+        # device path (tests inject one; None = ChannelRoots.roots on opts.job_device)
+        self._job_roots = None
+        self.job_roots_fn = None
+        self._branches_of: BlockTemplate | None = None  # the block whose merkle branches are cached below
+        self._branches: list[bytes] = []
         self._init_metrics(registry)
 
     # ------------------------------------------------------------ metrics
@@ -259,6 +270,8 @@ class PoolServer:
                 pass
         if self._batcher is not None:
             await self._batcher.close()  # pending submits are answered (on the CPU) before the journal closes
+        if self._job_roots is not None:
+            self._job_roots.close()
         self._hash_pool.shutdown(wait=False, cancel_futures=True)
         self.journal.close()
 
@@ -320,7 +333,7 @@ class PoolServer:
         self._job_counter += 1
         coinb1, coinb2 = self.block.coinbase_parts(EN1_SIZE + EN2_SIZE)
         job = PoolJob(self._job_counter, self.block, self.block.version, max(int(time.time()), self.block.ntime),
-                      coinb1, coinb2, self.block.branches(), clean)
+                      coinb1, coinb2, self._block_branches(), clean)
         self.jobs[job.job_id] = job
         self._seen[job.job_id] = set()
         while len(self.jobs) > 16:
@@ -328,9 +341,36 @@ class PoolServer:
             self._seen.pop(old, None)
         for c in list(self._v1):
             c.send_job(job)
-        for c in list(self._v2):
-            c.send_job(job)
+        v2 = list(self._v2)
+        roots = self._standard_roots(job, v2) if self.opts.job_device else {}
+        for c in v2:
+            c.send_job(job, roots.get(c))
         return job
+
+    def _block_branches(self) -> list[bytes]:
+        """The merkle branches of the current block, computed once per block: every job of a block shares them."""
+        if self._branches_of is not self.block:
+            self._branches_of, self._branches = self.block, self.block.branches()
+        return self._branches
+
+    def _standard_roots(self, job: PoolJob, conns: list) -> dict:
+        """connection -> {channel id -> merkle root} for every standard channel of ``conns``, all in one
+        ``JobRoots.roots`` call (pool/jobroots.py)."""
+        from otedama_amd.pool.batch import ShareJob
+
+        gathered = [(c, ch, prefix) for c in conns for ch, (_w, prefix) in c.channels.items()
+                    if ch not in c.extended]
+        if not gathered:
+            return {}
+        if self._job_roots is None:
+            from otedama_amd.pool.jobroots import JobRoots
+
+            self._job_roots = JobRoots(self, device_roots=self.job_roots_fn)
+        sj = ShareJob(job.coinb1, job.coinb2, EN1_SIZE + EN2_SIZE, job.block.prev_hash, job.block.nbits, job.branches)
+        out: dict = {}
+        for (c, ch, _prefix), root in zip(gathered, self._job_roots.roots(sj, [g[2] for g in gathered])):
+            out.setdefault(c, {})[ch] = root
+        return out
 
     def next_extranonce(self, size: int) -> bytes:
         self._en_counter += 1
@@ -622,6 +662,14 @@ class PoolServer:
         return {"device": self.opts.verify_device, "enabled": False, "batches": 0, "gpu_shares": 0, "cpu_shares": 0,
                 "last_batch": 0, "max_batch": 0, "device_errors": 0}
 
+    def jobs_stats(self) -> dict:
+        """The ``jobs`` object of /api/v1/pool: the job fan-out's device, whether the configured path is in use
+        (False when the feature is off, and after a device error has turned a GPU path off), and its counters."""
+        if self._job_roots is not None:
+            return self._job_roots.stats()
+        return {"device": self.opts.job_device, "enabled": False, "fanouts": 0, "gpu_channels": 0, "cpu_channels": 0,
+                "last_channels": 0, "last_ms": 0.0, "device_errors": 0}
+
     def stats(self) -> dict:
         now = time.monotonic()
         live = self._live_workers()
@@ -636,6 +684,7 @@ class PoolServer:
                             "p99": self.validation_ms(0.99), "samples": len(self._validate_ms)},
             "fixed_difficulty": self.opts.fixed_difficulty,
             "verify": self.verify_stats(),
+            "jobs": self.jobs_stats(),
             "new_block_at": list(self.new_block_at)[-64:],
             # per live connection: the difficulty in force, how often vardiff moved it, and when it last moved
             # (seconds after the channel opened: the time vardiff took to reach the difficulty it holds)
@@ -834,23 +883,27 @@ class _V2Conn:
         except Exception:  # noqa: BLE001
             pass
 
-    def _job_msgs(self, ch: int, job: PoolJob, prefix: bytes, future: bool) -> list[M.Message]:
+    def _job_msgs(self, ch: int, job: PoolJob, prefix: bytes, future: bool,
+                  root: bytes | None = None) -> list[M.Message]:
+        """``root``: the standard channel's merkle root if the caller already has it (the job fan-out)."""
         if ch in self.extended:
             j = M.NewExtendedMiningJob(ch, job.job_int, has_min_ntime=not future, min_ntime=0 if future else job.ntime,
                                        version=job.version, version_rolling_allowed=self.version_rolling,
                                        merkle_path=list(job.branches), coinbase_prefix=job.coinb1,
                                        coinbase_suffix=job.coinb2)
         else:
-            root = self.pool.merkle_root_for(job, prefix)
+            if root is None:
+                root = self.pool.merkle_root_for(job, prefix)
             j = M.NewMiningJob(ch, job.job_int, has_min_ntime=not future, min_ntime=0 if future else job.ntime,
                                version=job.version, merkle_root=root)
         if future:
             return [j, M.SetNewPrevHash(ch, job.job_int, job.block.prev_hash, job.ntime, job.block.nbits)]
         return [j]
 
-    def send_job(self, job: PoolJob) -> None:
+    def send_job(self, job: PoolJob, roots: dict | None = None) -> None:
+        """``roots``: channel id -> merkle root for the standard channels whose root is already computed."""
         for ch, (_w, prefix) in self.channels.items():
-            for m in self._job_msgs(ch, job, prefix, future=job.clean):
+            for m in self._job_msgs(ch, job, prefix, future=job.clean, root=roots.get(ch) if roots else None):
                 self._send(m)
 
     async def run(self) -> None:

@@ -1,7 +1,8 @@
 // Stand-alone host check of the share job block (csrc/cpu/share_job.cpp) for ASan + UBSan builds
 // (tools/sanitize/run.sh): share_job_prepare and share_headers_cpu over the length grid of
 // tests/test_share_verify_cpu.py, each header compared with a straightforward rebuild (sha256d of the whole
-// coinbase, the merkle fold, the packed header), plus the limit violations. Exit status 0 = all equal.
+// coinbase, the merkle fold, the packed header), share_roots_cpu's roots compared with those headers' roots, plus the
+// limit violations. Exit status 0 = all equal.
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
@@ -93,6 +94,16 @@ int main() {
               ++failures;
             }
           }
+          // share_roots_cpu on exactly sized heap buffers: prefix rows in, the merkle roots of the headers out
+          std::vector<uint8_t> rows(16 * recs.size()), roots(32 * recs.size());
+          for (size_t i = 0; i < recs.size(); ++i) std::memcpy(rows.data() + 16 * i, recs[i].extranonce, 16);
+          share_roots_cpu(job, rows.data(), recs.size(), roots.data());
+          for (size_t i = 0; i < recs.size(); ++i)
+            if (std::memcmp(roots.data() + 32 * i, out.data() + 80 * i + 36, 32) != 0) {
+              std::fprintf(stderr, "root mismatch: len1=%d en=%d len2=%d branches=%d prefix %zu\n", len1, en, len2, nb,
+                           i);
+              ++failures;
+            }
           ++jobs;
         }
 
