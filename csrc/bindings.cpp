@@ -115,6 +115,10 @@ py::dict stats_to_dict(const MinerStats& s) {
   d["error"] = s.error;
   d["variant_next"] = s.variant_next;
   d["variant_epoch"] = s.variant_epoch;
+  d["cursor_k"] = s.cursor_k;
+  d["cursor_nonce_off"] = s.cursor_nonce_off;
+  d["inflight"] = s.inflight;
+  d["idle"] = s.idle;
   d["job_switches"] = s.job_switches;
   d["last_job_switch_ms"] = s.last_job_switch_ms;
   d["job_switch_ms"] = s.job_switch_ms;

@@ -83,6 +83,16 @@ struct MinerStats {
   // so nothing is searched twice).
   uint64_t variant_next = 0;
   uint64_t variant_epoch = 0;
+  // The GPU miner's position inside its stripe, written with variant_next when a launch is queued (and when new work
+  // resets it): the next launch starts at nonce offset cursor_nonce_off of the group at stripe position cursor_k.
+  // Everything before it has been queued; it has been searched once `idle` is set. The CPU miner leaves these 0.
+  uint64_t cursor_k = 0;
+  uint64_t cursor_nonce_off = 0;
+  uint64_t inflight = 0;  // launches queued or running
+  // Set by the device thread when it has itself seen nothing in flight and nothing left to queue for the job that
+  // is set right now (a pause, or the stripe exhausted); cleared by every set_job() and by every launch queued.
+  // `inflight == 0` alone can be read between a launch retiring and the next one being queued; this cannot.
+  bool idle = false;
   // Job switches (GPU): set_job() of new work -> the first batch of that work running on the device, in ms.
   uint64_t job_switches = 0;
   double last_job_switch_ms = 0;
@@ -157,6 +167,8 @@ class MinerBase {
   std::shared_ptr<const JobTemplate> current_job(uint64_t* gen);
   // Non-blocking: the current job, its work generation and when that generation was set (monotonic seconds).
   std::shared_ptr<const JobTemplate> peek_job(uint64_t* gen, double* set_at);
+  // Sets stats().idle if `seen` (what the caller's idle observation was made for) is still the job that is set.
+  void mark_idle(const std::shared_ptr<const JobTemplate>& seen);
   std::string device_id_;
   ShareQueue queue_;
   std::mutex job_mu_;

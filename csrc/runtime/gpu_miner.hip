@@ -592,6 +592,7 @@ struct GpuMiner::Run {
     m.stats_.candidates += n;
     m.stats_.busy_seconds += ms * 1e-3;
     m.stats_.launches += 1;
+    m.stats_.inflight = fifo.size() - 1;  // both callers take this batch off the fifo next
     if (aborted) m.stats_.aborted_launches += 1;
     if (b.nvar > 1) m.stats_.variant_launches += 1;
     b.busy = false;
@@ -753,6 +754,10 @@ struct GpuMiner::Run {
     m.stats_.variant_epoch = job->epoch;
     m.stats_.launch_hashes = s.count * uint64_t(s.nvar);
     m.stats_.variant_next = cursor.variant_next(job->variant_start, job->variant_stride, group->nvar);
+    m.stats_.cursor_k = cursor.k;
+    m.stats_.cursor_nonce_off = cursor.nonce_off;
+    m.stats_.inflight = fifo.size() + 1;  // fill() puts this batch on the fifo next
+    m.stats_.idle = false;
   }
 
   bool retire_completed(const JobPtr& job, uint64_t gen) {
@@ -799,11 +804,15 @@ struct GpuMiner::Run {
     }
   }
 
+  // The cursor is past the last variant of this device's stripe.
+  bool stripe_exhausted(const JobTemplate& job) const {
+    return job.variant_start + cursor.k * job.variant_stride >= job.variant_space();
+  }
+
   bool fill(const JobPtr& job, uint64_t gen) {
     bool progressed = false;
     while (job && (int)fifo.size() < kInflight) {
-      const uint64_t v = job->variant_start + cursor.k * job->variant_stride;
-      if (v >= job->variant_space()) break;  // stripe exhausted: wait for fresh work
+      if (stripe_exhausted(*job)) break;  // wait for fresh work
       // scrypt halves: keep the two in flight half a hash apart (the second waits until the first is half way), so
       // their phase-boundary polls interleave; re-established after every switch
       if (job->algo == Algo::kScrypt && scrypt_halves && fifo.size() == 1) {
@@ -872,6 +881,9 @@ struct GpuMiner::Run {
       if (switch_pending) record_switch(job);
       // 4) keep kInflight batches queued
       progressed |= fill(job, gen);
+      // 5) nothing in flight and, for the job this trip looked at, nothing to queue: everything up to the cursor has
+      // been searched and its hits handed on (stats().idle; set_job() clears it again)
+      if (fifo.empty() && (!job || stripe_exhausted(*job))) m.mark_idle(job);
       if (!progressed) {
         if (!job && fifo.empty()) {
           uint64_t g2 = 0;

@@ -416,8 +416,19 @@ void MinerBase::set_job(std::shared_ptr<const JobTemplate> job) {
     if (job && !(last_work_ && same_work(*last_work_, *job))) ++job_gen_;
     if (job) last_work_ = job;
     job_ = std::move(job);
+    // stats().idle speaks about the job that is set: from here on only an observation made for this one counts
+    // (lock order: job_mu_, then stats_mu_; mark_idle takes them the same way round)
+    std::lock_guard<std::mutex> sg(stats_mu_);
+    stats_.idle = false;
   }
   job_cv_.notify_all();
+}
+
+void MinerBase::mark_idle(const std::shared_ptr<const JobTemplate>& seen) {
+  std::lock_guard<std::mutex> g(job_mu_);
+  if (job_ != seen) return;  // set_job() since the caller looked: its next look decides
+  std::lock_guard<std::mutex> sg(stats_mu_);
+  stats_.idle = true;
 }
 
 std::shared_ptr<const JobTemplate> MinerBase::current_job(uint64_t* gen) {

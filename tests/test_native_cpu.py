@@ -250,6 +250,18 @@ def test_cpu_miner_pause_with_none_job():
     m.stop()
 
 
+def test_miner_stats_export_the_search_cursor_and_idle():
+    """The GPU miner's cursor / quiescence fields are part of every miner's stats (tests/test_miner_exact_gpu.py
+    reads them on the device); a miner that never started reports them 0, and the CPU miner leaves them 0."""
+    fields = {"cursor_k": 0, "cursor_nonce_off": 0, "inflight": 0, "idle": False}
+    g = N.GpuMiner(0, "gpu-0")  # never started: no device is touched
+    g.set_job(_job(target=int_to_hash(1), epoch=1, job_id="a"))
+    assert {k: g.stats()[k] for k in fields} == fields
+    c = N.CpuMiner(1, "cpu-0")
+    c.set_job(None)
+    assert {k: c.stats()[k] for k in fields} == fields
+
+
 @pytest.mark.parametrize("start,count", [(0, 1), (7, 2), (11, 999), (0xFFFFFF00, 513)])
 def test_cpu_scan_pairs_and_tail_match_python(start, count):
     """The scan hashes nonces in interleaved pairs plus a scalar tail; any count/start (incl. the 2^32 wrap)
