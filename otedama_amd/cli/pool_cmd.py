@@ -63,7 +63,7 @@ def verify_options(fs: FlagSet) -> dict:
 
 
 def verify_options_error(opts: dict) -> str | None:
-    from otedama_amd.pool.microbatch import valid_device
+    from otedama_amd.pool.devicepath import valid_device
 
     if not valid_device(opts["verify_device"]):
         return f"--verify-device {opts['verify_device']!r} must be empty (off), cpu or cuda:N"
@@ -80,7 +80,7 @@ def job_options(fs: FlagSet) -> dict:
 
 
 def job_options_error(opts: dict) -> str | None:
-    from otedama_amd.pool.microbatch import valid_device
+    from otedama_amd.pool.devicepath import valid_device
 
     if not valid_device(opts["job_device"]):
         return f"--job-device {opts['job_device']!r} must be empty (off), cpu or cuda:N"

@@ -185,7 +185,7 @@ class Config:
         if self.pool_server.target_share_seconds <= 0:
             issues.append("pool_server.target_share_seconds must be > 0")
         ps = self.pool_server
-        from otedama_amd.pool.microbatch import valid_device  # torch-free; the one statement of the device grammar
+        from otedama_amd.pool.devicepath import valid_device  # torch-free; the one statement of the device grammar
 
         if not valid_device(str(ps.verify_device)):
             issues.append(f"pool_server.verify_device {ps.verify_device!r} is not one of \"\", cpu, cuda:N")

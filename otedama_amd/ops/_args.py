@@ -6,6 +6,15 @@ import torch
 ALIGN = 16  # the kernels move headers, digests, records and targets as 16-byte vectors
 
 
+def gpu_device(device, who: str) -> torch.device:
+    """``device`` as a CUDA ``torch.device`` with its index resolved (the current device when it names none);
+    ``ValueError`` naming ``who`` for any other kind of device."""
+    d = torch.device(device)
+    if d.type != "cuda":
+        raise ValueError(f"{who} needs a GPU device")
+    return d if d.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
 def byte_rows(name: str, t, width: int, device: torch.device, rows: int | None = None) -> int:
     """Check that ``t`` is a contiguous uint8 ``[n, width]`` tensor on ``device`` (``n == rows`` if given) that
     starts at a 16-byte aligned address unless it is empty, and return ``n``. Anything else raises ``ValueError``

@@ -17,7 +17,7 @@ from typing import Sequence
 import torch
 
 from otedama_amd.models import algorithms
-from otedama_amd.ops._args import ALIGN, byte_rows, launch_stream  # noqa: F401  (ALIGN: for importers of this module)
+from otedama_amd.ops._args import ALIGN, byte_rows, gpu_device, launch_stream  # noqa: F401  (ALIGN: for importers)
 from otedama_amd.ops.native import require_native
 from otedama_amd.ops.search import default_grid
 from otedama_amd.ops.tuning import SCRYPT_BLOCKS_PER_CU
@@ -39,11 +39,7 @@ class HeaderDigest:
         ``ScryptSearch``; a given ``capacity`` is rounded up to whole blocks."""
         self.algorithm = algorithms.get(algorithm).name
         self.native = require_native()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("HeaderDigest needs a GPU device")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = gpu_device(device, "HeaderDigest")
         if capacity is not None and capacity <= 0:
             raise ValueError("capacity must be positive")
         if grid is not None and grid <= 0:

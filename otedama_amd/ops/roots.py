@@ -12,7 +12,8 @@ from typing import Sequence
 
 import torch
 
-from otedama_amd.ops._args import byte_rows, launch_stream
+from otedama_amd.ops._args import byte_rows, gpu_device, launch_stream
+from otedama_amd.ops._staging import Staging
 from otedama_amd.ops.native import require_native
 from otedama_amd.ops.share_records import PREFIX_BYTES, ROOT_BYTES, pack_prefixes, unpack_roots  # noqa: F401
 from otedama_amd.ops.verify import PreparedJob, check_prepared, prepare_job
@@ -23,15 +24,8 @@ class ChannelRoots:
 
     def __init__(self, device="cuda:0"):
         self.native = require_native()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("ChannelRoots needs a GPU device")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self._pin_in: torch.Tensor | None = None   # pinned: prefix rows
-        self._dev_in: torch.Tensor | None = None
-        self._pin_out: torch.Tensor | None = None  # pinned: roots
-        self._dev_out: torch.Tensor | None = None
+        self.device = gpu_device(device, "ChannelRoots")
+        self._staging = Staging(self.device)  # in: prefix rows, out: roots
 
     def prepare(self, coinb1: bytes, coinb2: bytes, en_size: int, prev_hash: bytes, nbits: int,
                 branches: Sequence[bytes]) -> PreparedJob:
@@ -63,15 +57,6 @@ class ChannelRoots:
                                          stream.cuda_stream)
         return out
 
-    def _grown(self, name: str, nbytes: int, pinned: bool) -> torch.Tensor:
-        buf = getattr(self, name)
-        if buf is None or buf.numel() < nbytes:
-            size = max(nbytes, 2 * buf.numel() if buf is not None else 4096)
-            buf = (torch.empty(size, dtype=torch.uint8, pin_memory=True) if pinned
-                   else torch.empty(size, dtype=torch.uint8, device=self.device))
-            setattr(self, name, buf)
-        return buf
-
     def roots(self, job: PreparedJob, prefixes: Sequence[bytes]) -> list[bytes]:
         """The pool's entry: ``en_size``-byte prefixes in, their 32-byte roots out, in order. One pinned buffer of
         prefix rows goes to the device and one pinned buffer of roots comes back, both copies non-blocking on the
@@ -81,13 +66,6 @@ class ChannelRoots:
         n = len(prefixes)
         if n == 0:
             return []
-        in_bytes, out_bytes = n * PREFIX_BYTES, n * ROOT_BYTES
-        pin_in, dev_in = self._grown("_pin_in", in_bytes, True), self._grown("_dev_in", in_bytes, False)
-        pin_out, dev_out = self._grown("_pin_out", out_bytes, True), self._grown("_dev_out", out_bytes, False)
-        memoryview(pin_in.numpy())[:in_bytes] = packed
-        stream = torch.cuda.current_stream(self.device)
-        dev_in[:in_bytes].copy_(pin_in[:in_bytes], non_blocking=True)
-        self.launch(job, dev_in[:in_bytes].view(n, PREFIX_BYTES), out=dev_out[:out_bytes].view(n, ROOT_BYTES))
-        pin_out[:out_bytes].copy_(dev_out[:out_bytes], non_blocking=True)
-        stream.synchronize()
-        return unpack_roots(memoryview(pin_out.numpy())[:out_bytes])
+        return unpack_roots(self._staging.round_trip(
+            [packed], n * ROOT_BYTES,
+            lambda dev_in, dev_out: self.launch(job, dev_in.view(n, PREFIX_BYTES), out=dev_out.view(n, ROOT_BYTES))))

@@ -24,6 +24,7 @@ from typing import Sequence
 import torch
 
 from otedama_amd.ops._args import ALIGN, byte_rows, launch_stream
+from otedama_amd.ops._staging import Staging
 from otedama_amd.ops.digest import DIGEST_BYTES, HEADER_BYTES, HeaderDigest
 from otedama_amd.ops.share_records import (MAX_EXTRANONCE, RECORD_BYTES, RESULT_BYTES, VERDICT_BAD_INDEX,  # noqa: F401
                                            VERDICT_NETWORK, VERDICT_SHARE, pack_records, unpack_records,
@@ -74,10 +75,7 @@ class ShareVerify:
         # the live path (launch_results / results): the digests between the chain and the pack kernel, and the
         # staging buffers of results(), all grown to the largest batch seen
         self._digests: torch.Tensor | None = None
-        self._pin_in: torch.Tensor | None = None   # pinned: records | targets
-        self._dev_in: torch.Tensor | None = None
-        self._pin_out: torch.Tensor | None = None  # pinned: result records
-        self._dev_out: torch.Tensor | None = None
+        self._staging = Staging(self.device)  # in: records | targets, out: result records
 
     def prepare(self, coinb1: bytes, coinb2: bytes, en_size: int, prev_hash: bytes, nbits: int,
                 branches: Sequence[bytes]) -> PreparedJob:
@@ -164,15 +162,6 @@ class ShareVerify:
                                       targets.data_ptr(), targets.shape[0], n, out.data_ptr(), stream.cuda_stream)
         return out
 
-    def _grown(self, name: str, nbytes: int, pinned: bool) -> torch.Tensor:
-        buf = getattr(self, name)
-        if buf is None or buf.numel() < nbytes:
-            size = max(nbytes, 2 * buf.numel() if buf is not None else 4096)
-            buf = (torch.empty(size, dtype=torch.uint8, pin_memory=True) if pinned
-                   else torch.empty(size, dtype=torch.uint8, device=self.device))
-            setattr(self, name, buf)
-        return buf
-
     @staticmethod
     def _packed(job: PreparedJob, shares: Sequence[tuple], targets: Sequence[bytes],
                 target_indices: Sequence[int] | None) -> tuple[bytes, bytes, int]:
@@ -196,21 +185,13 @@ class ShareVerify:
         n = len(shares)
         if n == 0:
             return []
-        rec_bytes, out_bytes = n * RECORD_BYTES, n * RESULT_BYTES
-        in_bytes = rec_bytes + n_targets * TARGET_BYTES
-        pin_in, dev_in = self._grown("_pin_in", in_bytes, True), self._grown("_dev_in", in_bytes, False)
-        pin_out, dev_out = self._grown("_pin_out", out_bytes, True), self._grown("_dev_out", out_bytes, False)
-        host = memoryview(pin_in.numpy())
-        host[:rec_bytes] = packed
-        host[rec_bytes:in_bytes] = table
-        stream = torch.cuda.current_stream(self.device)
-        dev_in[:in_bytes].copy_(pin_in[:in_bytes], non_blocking=True)
-        out = dev_out[:out_bytes].view(n, RESULT_BYTES)
-        self.launch_results(job, dev_in[:rec_bytes].view(n, RECORD_BYTES),
-                            dev_in[rec_bytes:in_bytes].view(n_targets, TARGET_BYTES), out=out)
-        pin_out[:out_bytes].copy_(dev_out[:out_bytes], non_blocking=True)
-        stream.synchronize()
-        return unpack_results(memoryview(pin_out.numpy())[:out_bytes])
+        rec_bytes = n * RECORD_BYTES
+
+        def launch(dev_in: torch.Tensor, dev_out: torch.Tensor) -> None:
+            self.launch_results(job, dev_in[:rec_bytes].view(n, RECORD_BYTES),
+                                dev_in[rec_bytes:].view(n_targets, TARGET_BYTES), out=dev_out.view(n, RESULT_BYTES))
+
+        return unpack_results(self._staging.round_trip([packed, table], n * RESULT_BYTES, launch))
 
     def verify(self, job: PreparedJob, shares: Sequence[tuple], targets: Sequence[bytes],
                target_indices: Sequence[int] | None = None) -> tuple[list[int], list[bytes], list[bytes]]:

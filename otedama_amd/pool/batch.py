@@ -32,8 +32,24 @@ class ShareJob:
     branches: list = field(default_factory=list)
 
 
-_verify_ops: dict[tuple[str, str], object] = {}  # (algorithm, device) -> ops.verify.ShareVerify
-_roots_ops: dict[str, object] = {}  # device -> ops.roots.ChannelRoots
+_ops: dict[tuple, object] = {}  # (kind, algorithm, device) -> ops.verify.ShareVerify or ops.roots.ChannelRoots
+
+
+def prepared_or_none(prepare, job: ShareJob):
+    """``prepare`` (an op's, or the native ``share_job_prepare``) of ``job``'s block, or ``None`` for a job over the
+    block's limits: that job is the CPU's."""
+    try:
+        return prepare(job.coinb1, job.coinb2, job.en_size, job.prev_hash, job.nbits & 0xFFFFFFFF, list(job.branches))
+    except ValueError:
+        return None
+
+
+def _op_and_block(key: tuple, make_op, job: ShareJob):
+    """The process's op for ``key`` (made on first use) and ``job``'s block prepared on its device, or ``None``."""
+    op = _ops.get(key)
+    if op is None:
+        op = _ops[key] = make_op()
+    return op, prepared_or_none(op.prepare, job)
 
 
 def root_of(job: ShareJob, extranonce: bytes) -> bytes:
@@ -68,15 +84,8 @@ def check_shares(algorithm: str, job: ShareJob, shares: Sequence[tuple], targets
     if device is not None and shares:
         from otedama_amd.ops.verify import ShareVerify  # imports torch
 
-        key = (algo.name, str(device))
-        op = _verify_ops.get(key)
-        if op is None:
-            op = _verify_ops[key] = ShareVerify(algo.name, device)
-        try:
-            prepared = op.prepare(job.coinb1, job.coinb2, job.en_size, job.prev_hash, job.nbits, job.branches)
-        except ValueError:
-            prepared = None  # over the block's limits: the oracle path below
-        if prepared is not None:
+        op, prepared = _op_and_block(("verify", algo.name, str(device)), lambda: ShareVerify(algo.name, device), job)
+        if prepared is not None:  # else over the block's limits: the oracle path below
             verdicts, hashes, headers = op.verify(prepared, shares, targets, target_indices)
             return list(zip(headers, hashes, verdicts))
     out = []
@@ -103,28 +112,18 @@ def channel_roots(job: ShareJob, prefixes: Sequence[bytes], device=None) -> list
         if len(p) != job.en_size:
             raise ValueError(f"prefix {i} is {len(p)} bytes, the job takes {job.en_size}")
     if device is not None and prefixes:
-        args = (job.coinb1, job.coinb2, job.en_size, job.prev_hash, job.nbits & 0xFFFFFFFF, list(job.branches))
         if str(device) == "cpu":
             from otedama_amd.ops.native import require_native
             from otedama_amd.ops.share_records import pack_prefixes, unpack_roots
 
             native = require_native()
-            try:
-                block = native.share_job_prepare(*args)
-            except ValueError:
-                block = None  # over the block's limits: the Python path below
-            if block is not None:
+            block = prepared_or_none(native.share_job_prepare, job)
+            if block is not None:  # else over the block's limits: the Python path below
                 return unpack_roots(native.share_roots_cpu(block, pack_prefixes(prefixes, job.en_size)))
         else:
             from otedama_amd.ops.roots import ChannelRoots  # imports torch
 
-            op = _roots_ops.get(str(device))
-            if op is None:
-                op = _roots_ops[str(device)] = ChannelRoots(device)
-            try:
-                prepared = op.prepare(*args)
-            except ValueError:
-                prepared = None  # as above
-            if prepared is not None:
+            op, prepared = _op_and_block(("roots", "", str(device)), lambda: ChannelRoots(device), job)
+            if prepared is not None:  # as above
                 return op.roots(prepared, prefixes)
     return [root_of(job, p) for p in prefixes]

@@ -9,8 +9,8 @@ touched there, and importing this module imports neither. With ``job_device="cpu
 
 Fallbacks: a fan-out of fewer channels than ``job_min_gpu`` goes to the native CPU path, a job over the job block's
 limits to Python (inside ``channel_roots``). Any exception from the device path sends that fan-out to the CPU, is
-logged and counted, and puts the device into ``microbatch._failed_devices``, the process-wide switch the share
-verifier uses: a GPU that has faulted for either path is used by neither again.
+logged and counted, and turns the device off in ``pool.devicepath``, the process-wide switch the share verifier
+uses too: a GPU that has faulted for either path is used by neither again.
 
 The device call has no time limit: one that never returns (a hung GPU) holds ``_make_job``, and with it the event
 loop, for good. A blocked ``hipStreamSynchronize`` cannot be abandoned safely from Python, so none is attempted.
@@ -20,9 +20,8 @@ from __future__ import annotations
 import concurrent.futures
 import time
 
-from otedama_amd.pool import microbatch
 from otedama_amd.pool.batch import channel_roots
-from otedama_amd.pool.microbatch import device_failed, valid_device
+from otedama_amd.pool.devicepath import DevicePath
 
 # job_min_gpu = 0 resolves to this: the smallest measured fan-out, rounded up to a power of two, at which the GPU
 # round trip (ChannelRoots.roots, p50) was at or below the same host's channel_roots(device="cpu") time
@@ -36,29 +35,22 @@ class JobRoots:
         """``pool``: the PoolServer, whose ``opts.job_*`` configure the fan-out. ``device_roots``: replaces the GPU
         path, ``device_roots(job, prefixes)`` called on the worker thread."""
         o = pool.opts
-        if not valid_device(o.job_device) or not o.job_device:
-            raise ValueError(f"job_device {o.job_device!r} must be cpu or cuda:N")
+        self.path = DevicePath("job_device", o.job_device)
         if o.job_min_gpu < 0:
             raise ValueError("job_min_gpu must not be negative")
         self.pool = pool
-        self.device = o.job_device
+        self.device = self.path.device
         self.min_gpu = int(o.job_min_gpu) or DEFAULT_JOB_MIN_GPU
         self._device_roots = device_roots
-        self._gpu = self.device != "cpu"
         self._worker = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="otedama-pool-job")
-        self.fanouts = self.gpu_channels = self.cpu_channels = self.last_channels = self.device_errors = 0
+        self.fanouts = self.gpu_channels = self.cpu_channels = self.last_channels = 0
         self.last_ms = 0.0
 
-    @property
-    def _device_on(self) -> bool:
-        return self._gpu and not device_failed(self.device)
-
     def stats(self) -> dict:
-        # enabled: the configured path is in use (False once a device error, of this fan-out or of a share verifier
-        # of the process on the same device, has turned the GPU path off)
-        return {"device": self.device, "enabled": self._device_on or not self._gpu, "fanouts": self.fanouts,
+        return {"device": self.device, "enabled": self.path.enabled, "fanouts": self.fanouts,
                 "gpu_channels": self.gpu_channels, "cpu_channels": self.cpu_channels,
-                "last_channels": self.last_channels, "last_ms": self.last_ms, "device_errors": self.device_errors}
+                "last_channels": self.last_channels, "last_ms": self.last_ms,
+                "device_errors": self.path.device_errors}
 
     def close(self) -> None:
         self._worker.shutdown(wait=True)
@@ -68,10 +60,9 @@ class JobRoots:
         if not prefixes:
             return []
         t0 = time.perf_counter()
-        on_device = self._device_on and len(prefixes) >= self.min_gpu
+        on_device = self.path.on and len(prefixes) >= self.min_gpu
         roots, on_gpu, error = self._worker.submit(self._compute, job, prefixes, on_device).result()
-        if error is not None:  # the worker thread has already put the device on the failed list
-            self.device_errors += 1
+        if error is not None:  # the worker thread has already counted it and put the device on the failed list
             pool = self.pool
             pool.log("error", f"pool[{pool.algo.name}]: job fan-out on {self.device} failed ({error!r}); the roots "
                               f"were computed on the CPU and the device path is off for this process")
@@ -84,13 +75,12 @@ class JobRoots:
 
     def _compute(self, job, prefixes: list, on_device: bool):
         """On the worker thread: ``(roots, channels computed on the device, device error)``."""
-        if on_device and not device_failed(self.device):  # a share verifier may have failed since the loop looked
-            try:
-                if self._device_roots is not None:
-                    return self._device_roots(job, prefixes), len(prefixes), None
-                # a job over the block's limits is computed in Python there; it is still counted with the device
-                return channel_roots(job, prefixes, self.device), len(prefixes), None
-            except Exception as exc:  # noqa: BLE001 - whatever the device path raised, the job still goes out
-                microbatch._failed_devices.add(self.device)
-                return channel_roots(job, prefixes, "cpu"), 0, exc
-        return channel_roots(job, prefixes, "cpu"), 0, None
+        def cpu():
+            return channel_roots(job, prefixes, "cpu")
+
+        if not on_device:
+            return cpu(), 0, None
+        # a job over the block's limits is computed in Python inside channel_roots; it is still counted with the device
+        device = self._device_roots or (lambda j, p: channel_roots(j, p, self.device))
+        roots, ran, error = self.path.run(lambda: device(job, prefixes), cpu)
+        return roots, len(prefixes) if ran else 0, error

@@ -16,8 +16,9 @@ and importing this module imports neither. With ``verify_device="cpu"`` the thre
 Fallbacks: a flush with fewer survivors than ``verify_min_gpu`` and a job over the job block's limits are hashed on
 the CPU. Any exception from the device path sends that batch to the CPU, is logged and counted, and turns the device
 path off for the rest of the process: a GPU that has faulted is not used again, by this batcher or by any other in
-the process (``otedama pool --algorithms a,b`` runs one pool and one batcher per algorithm on the same device; the
-switch is the module's, per device). ``close()`` flushes what is pending on the CPU and resolves every future.
+the process, nor by the job fan-out (the switch is ``pool.devicepath``'s, per device; the batcher's share of it is
+its :class:`~otedama_amd.pool.devicepath.DevicePath`). ``close()`` flushes what is pending on the CPU and resolves
+every future.
 
 Stage 2 has no time limit: a device call that never returns (a hung GPU) holds its batch, every later submit and
 ``close()``. A blocked ``hipStreamSynchronize`` cannot be abandoned safely from Python, so none is attempted.
@@ -26,39 +27,18 @@ from __future__ import annotations
 
 import asyncio
 import concurrent.futures
-import re
 import time
 from collections import deque
 
-from otedama_amd.pool.batch import check_shares
+from otedama_amd.pool.batch import check_shares, prepared_or_none
+from otedama_amd.pool.devicepath import (DevicePath, device_failed, forget_device_errors,  # noqa: F401 - re-exported
+                                         valid_device)
 
 # verify_min_gpu = 0 resolves to these: the smallest measured batch, rounded up to a power of two, at which the GPU
 # round trip (ShareVerify.results, p50) was at or below the same host's check_shares(device=None) time
 # (tools/bench_verify_live.py; the table is in docs/POOL.md).
 NEVER = 1 << 31  # above any batch: the GPU never won up to 4096 shares
 DEFAULT_MIN_GPU = {"sha256d": 64, "scrypt": 64, "x11": 8}
-
-_DEVICE_RE = re.compile(r"^(cpu|cuda:\d+)$")
-
-
-def valid_device(device: str) -> bool:
-    """``""`` (off), ``cpu`` or ``cuda:N``. The one statement of the grammar: config.py and the CLI ask here."""
-    return device == "" or bool(_DEVICE_RE.match(device))
-
-
-# Devices whose path raised in this process. Every batcher looks here before it chooses the device, on the event
-# loop and again on its worker thread, so after one pool's device error no other pool of the process starts a call
-# on that device. Nothing in the package takes a device out again.
-_failed_devices: set = set()
-
-
-def device_failed(device: str) -> bool:
-    return device in _failed_devices
-
-
-def forget_device_errors() -> None:
-    """For tests that inject a failure: a later test in the same process gets its device back."""
-    _failed_devices.clear()
 
 
 class DeviceHasher:
@@ -79,11 +59,7 @@ class DeviceHasher:
         if key not in self._prepared:
             while len(self._prepared) >= self.KEEP_JOBS:
                 self._prepared.pop(next(iter(self._prepared)))
-            try:
-                self._prepared[key] = self.op.prepare(job.coinb1, job.coinb2, job.en_size, job.prev_hash, job.nbits,
-                                                      job.branches)
-            except ValueError:
-                self._prepared[key] = None  # over the block's limits: this job is the CPU's
+            self._prepared[key] = prepared_or_none(self.op.prepare, job)
         return self._prepared[key]
 
     def takes(self, job) -> bool:
@@ -103,34 +79,26 @@ class ShareBatcher:
         GPU path, ``hasher(job, shares, targets, target_indices)`` called on the worker thread; if it has a
         ``takes(job)`` method, a group it does not take is hashed and counted on the CPU."""
         o = pool.opts
-        if not valid_device(o.verify_device) or not o.verify_device:
-            raise ValueError(f"verify_device {o.verify_device!r} must be cpu or cuda:N")
+        self.path = DevicePath("verify_device", o.verify_device)
         if o.verify_batch_ms <= 0 or o.verify_batch_max < 1 or o.verify_min_gpu < 0:
             raise ValueError("verify_batch_ms and verify_batch_max must be positive, verify_min_gpu not negative")
         self.pool = pool
-        self.device = o.verify_device
+        self.device = self.path.device
         self.batch_s = o.verify_batch_ms / 1e3
         self.batch_max = int(o.verify_batch_max)
         self.min_gpu = int(o.verify_min_gpu) or DEFAULT_MIN_GPU.get(pool.algo.name, NEVER)
         self._device_hasher = device_hasher
-        self._gpu = self.device != "cpu"
         self._pending: deque = deque()  # (item, future, t_received)
         self._wake = asyncio.Event()
         self._closing = False
         self._worker = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="otedama-pool-verify")
         self._task = asyncio.ensure_future(self._run())
-        self.batches = self.gpu_shares = self.cpu_shares = self.last_batch = self.max_batch = self.device_errors = 0
-
-    @property
-    def _device_on(self) -> bool:
-        return self._gpu and not device_failed(self.device)
+        self.batches = self.gpu_shares = self.cpu_shares = self.last_batch = self.max_batch = 0
 
     def stats(self) -> dict:
-        # enabled: the configured path is in use (False once a device error, in this pool or in another pool of the
-        # process on the same device, has turned the GPU path off)
-        return {"device": self.device, "enabled": self._device_on or not self._gpu, "batches": self.batches,
+        return {"device": self.device, "enabled": self.path.enabled, "batches": self.batches,
                 "gpu_shares": self.gpu_shares, "cpu_shares": self.cpu_shares, "last_batch": self.last_batch,
-                "max_batch": self.max_batch, "device_errors": self.device_errors}
+                "max_batch": self.max_batch, "device_errors": self.path.device_errors}
 
     async def submit(self, item: tuple, t_received: float):
         """``item``: ``(worker, job_id, extranonce, ntime, nonce, version)``; ``t_received``: ``time.perf_counter()``
@@ -177,11 +145,10 @@ class ShareBatcher:
             checked = pool._check_fields(items)
             plan = pool._group_survivors(items, checked)
             survivors = sum(len(g[1]) for g in plan)
-            on_device = self._device_on and not self._closing and survivors >= self.min_gpu
+            on_device = self.path.on and not self._closing and survivors >= self.min_gpu
             hashed, on_gpu, error = await asyncio.get_running_loop().run_in_executor(
                 self._worker, self._hash, plan, on_device)
-            if error is not None:  # the worker thread has already put the device on the failed list
-                self.device_errors += 1
+            if error is not None:  # the worker thread has already counted it and put the device on the failed list
                 pool.log("error", f"pool[{pool.algo.name}]: share verification on {self.device} failed ({error!r}); "
                                   f"the batch was hashed on the CPU and the device path is off for this process")
             self.batches += 1
@@ -209,24 +176,23 @@ class ShareBatcher:
         def cpu(job, shares, targets, tidx):
             return check_shares(algorithm, job, shares, targets, tidx)
 
-        if on_device and not device_failed(self.device):  # another pool may have failed since the loop looked
-            on_gpu = 0
-            try:
-                if self._device_hasher is None:
-                    self._device_hasher = DeviceHasher(algorithm, self.device)
-                hasher = self._device_hasher
-                takes = getattr(hasher, "takes", None)
+        if not on_device:
+            return self.pool._hash_groups(plan, cpu), 0, None
+        on_gpu = 0
 
-                def dev(job, shares, targets, tidx):
-                    nonlocal on_gpu
-                    if takes is not None and not takes(job):
-                        return cpu(job, shares, targets, tidx)
-                    res = hasher(job, shares, targets, tidx)
-                    on_gpu += len(shares)
-                    return res
+        def dev(job, shares, targets, tidx):
+            nonlocal on_gpu
+            takes = getattr(self._device_hasher, "takes", None)
+            if takes is not None and not takes(job):
+                return cpu(job, shares, targets, tidx)
+            res = self._device_hasher(job, shares, targets, tidx)
+            on_gpu += len(shares)
+            return res
 
-                return self.pool._hash_groups(plan, dev), on_gpu, None
-            except Exception as exc:  # noqa: BLE001 - whatever the device path raised, the batch is still answered
-                _failed_devices.add(self.device)
-                return self.pool._hash_groups(plan, cpu), 0, exc
-        return self.pool._hash_groups(plan, cpu), 0, None
+        def on_dev():
+            if self._device_hasher is None:
+                self._device_hasher = DeviceHasher(algorithm, self.device)
+            return self.pool._hash_groups(plan, dev)
+
+        hashed, ran, error = self.path.run(on_dev, lambda: self.pool._hash_groups(plan, cpu))
+        return hashed, on_gpu if ran else 0, error

@@ -221,7 +221,7 @@ def test_a_failing_device_path_still_sends_the_right_roots_and_turns_the_device_
         vpool = R.seeded_pool(verify_device="cuda:0", verify_min_gpu=1)
         b = vpool._get_batcher()
         try:
-            return b._device_on, vpool.stats()["verify"]["enabled"]
+            return b.path.on, vpool.stats()["verify"]["enabled"]
         finally:
             await b.close()
             _dispose(vpool)
@@ -341,6 +341,9 @@ def test_batch_module_stays_torch_free_at_import():
     import sys
 
     code = ("import sys; import otedama_amd.pool.batch, otedama_amd.pool.jobroots, otedama_amd.ops.share_records; "
+            "assert 'torch' not in sys.modules and 'otedama_amd._native' not in sys.modules")
+    assert subprocess.run([sys.executable, "-c", code]).returncode == 0
+    code = ("import sys; import otedama_amd.pool.devicepath; "
             "assert 'torch' not in sys.modules and 'otedama_amd._native' not in sys.modules")
     assert subprocess.run([sys.executable, "-c", code]).returncode == 0
     assert batch.root_of(C.pool_job(), bytes(8)) == R.oracle_root(C.pool_job(), bytes(8))

@@ -154,9 +154,9 @@ def test_out_given_and_not_given_and_an_empty_batch():
     assert op.roots(prep, []) == []
     # the staging buffers of roots() are pinned, reused, and grow
     assert op.roots(prep, prefixes[:3]) == want[:3]
-    pin = op._pin_in
-    assert pin.is_pinned() and op._pin_out.is_pinned()
-    assert op.roots(prep, prefixes[:5]) == want[:5] and op._pin_in is pin
+    pin = op._staging.pin_in
+    assert pin.is_pinned() and op._staging.pin_out.is_pinned()
+    assert op.roots(prep, prefixes[:5]) == want[:5] and op._staging.pin_in is pin
     assert op.roots(prep, prefixes) == want
     with pytest.raises(ValueError):
         op.roots(prep, [bytes(job.en_size + 1)])

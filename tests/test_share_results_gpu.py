@@ -162,11 +162,11 @@ def test_results_equals_the_oracle_and_reuses_its_buffers():
         assert op.results(prep, shares, targets, indices) == want
         assert op.results(prep, shares[:1], targets[:1], None) == want[:1]
     assert op.results(prep, [], targets) == []
-    pin = op._pin_in
-    assert pin.is_pinned() and op._pin_out.is_pinned()
+    pin = op._staging.pin_in
+    assert pin.is_pinned() and op._staging.pin_out.is_pinned()
     job, shares, targets, indices, want = _sized_case(0)
     assert op.results(_prepare(op, job), shares[:5], targets, indices[:5]) == want[:5]
-    assert op._pin_in is pin  # no new staging buffer for a batch that fits
+    assert op._staging.pin_in is pin  # no new staging buffer for a batch that fits
     with pytest.raises(ValueError):
         op.results(prep, shares[:1], [], [0])
 
