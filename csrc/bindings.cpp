@@ -610,6 +610,30 @@ PYBIND11_MODULE(_native, m) {
     py_launch_channel_roots(job, prefixes, n, roots, stream);
   }, py::arg("job"), py::arg("prefixes"), py::arg("n"), py::arg("roots"), py::arg("stream") = 0);
 
+  // Template tree: t trees of n 32-byte leaves -> 1 + depth rows of 32 bytes per tree (otedama/merkle_tree.h).
+  m.def("merkle_tree_cpu", [](const py::bytes& leaves, uint32_t t, uint32_t n) {
+    if (t == 0 || t > kMerkleTreeMaxTrees) throw std::invalid_argument("t must be in 1..65535");
+    if (n == 0 || n > kMerkleTreeMaxLeaves) throw std::invalid_argument("n must be in 1..262144");
+    std::string ls = need(leaves, size_t(t) * n * 32, "leaves");
+    std::string out(size_t(t) * (1 + merkle_tree_depth(n)) * 32, '\0');
+    {
+      py::gil_scoped_release r;  // a full template is thousands of leaves in two trees
+      merkle_tree_cpu(reinterpret_cast<const uint8_t*>(ls.data()), t, n, reinterpret_cast<uint8_t*>(&out[0]));
+    }
+    return py::bytes(out);
+  }, py::arg("leaves"), py::arg("t"), py::arg("n"));
+  m.attr("MERKLE_TREE_MAX_LEAVES") = kMerkleTreeMaxLeaves;
+  m.attr("MERKLE_TREE_MAX_TREES") = kMerkleTreeMaxTrees;
+  m.def("launch_merkle_tree", [](uintptr_t leaves, uint32_t t, uint32_t n, uintptr_t scratch, uintptr_t out,
+                                 uintptr_t stream) {
+    if (t == 0 || t > kMerkleTreeMaxTrees || n == 0 || n > kMerkleTreeMaxLeaves)
+      throw std::invalid_argument("need t in 1..65535, n in 1..262144");
+    if (leaves == 0 || out == 0 || (n > 512 && scratch == 0))
+      throw std::invalid_argument("need leaves, out != 0, and scratch != 0 for n > 512");
+    if ((leaves | out | scratch) & 15u) throw std::invalid_argument("leaves, scratch and out must be 16-byte aligned");
+    py_launch_merkle_tree(leaves, t, n, scratch, out, stream);
+  }, py::arg("leaves"), py::arg("t"), py::arg("n"), py::arg("scratch"), py::arg("out"), py::arg("stream") = 0);
+
   py::class_<MinerBase, std::shared_ptr<MinerBase>>(m, "Miner")
       .def("start", &MinerBase::start, py::call_guard<py::gil_scoped_release>())
       .def("stop", &MinerBase::stop, py::call_guard<py::gil_scoped_release>())

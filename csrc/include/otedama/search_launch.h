@@ -8,6 +8,7 @@
 
 #include "otedama/hitsink.h"
 #include "otedama/job.h"
+#include "otedama/merkle_tree.h"
 
 namespace otedama {
 
@@ -60,6 +61,13 @@ void py_launch_share_pack(uintptr_t job, uintptr_t records, uintptr_t headers, u
 // Same conventions as above; every array is 16-byte aligned.
 void py_launch_channel_roots(uintptr_t job, uintptr_t prefixes, uint32_t n, uintptr_t roots, uintptr_t stream);
 
+// Template tree (otd_merkle_tree of merkle_tree.hip; rows, limits and the CPU twin: otedama/merkle_tree.h): t trees of
+// n 32-byte leaves at leaves + 32 * n * y -> 1 + depth rows of 32 bytes per tree at out + 32 * (1 + depth) * y.
+// scratch: 32 bytes per 512-leaf chunk per tree (t * ceil(n / 512) rows), read only when n > 512; may be 0 otherwise.
+// Same conventions as above; every array is 16-byte aligned.
+void py_launch_merkle_tree(uintptr_t leaves, uint32_t t, uint32_t n, uintptr_t scratch, uintptr_t out,
+                           uintptr_t stream);
+
 }  // namespace otedama
 
 #ifdef __HIPCC__
@@ -106,6 +114,10 @@ hipError_t launch_share_pack(const void* job, const uint8_t* records, const uint
 // Channel roots: hipErrorInvalidValue, before launching anything, for n == 0, a null pointer or an array (the job
 // block included) that is not 16-byte aligned.
 hipError_t launch_channel_roots(const void* job, const uint8_t* prefixes, uint32_t n, uint8_t* roots, hipStream_t s);
+// Template tree: hipErrorInvalidValue, before launching anything, for t == 0 or above kMerkleTreeMaxTrees, n == 0 or
+// above kMerkleTreeMaxLeaves, a null or not 16-byte aligned leaves or out, and the same of scratch when n > 512.
+hipError_t launch_merkle_tree(const uint8_t* leaves, uint32_t t, uint32_t n, uint8_t* scratch, uint8_t* out,
+                              hipStream_t s);
 
 }  // namespace otedama
 #endif

@@ -113,4 +113,11 @@ void py_launch_channel_roots(uintptr_t job, uintptr_t prefixes, uint32_t n, uint
             "launch_channel_roots");
 }
 
+void py_launch_merkle_tree(uintptr_t leaves, uint32_t t, uint32_t n, uintptr_t scratch, uintptr_t out,
+                           uintptr_t stream) {
+  hip_check(launch_merkle_tree(reinterpret_cast<const uint8_t*>(leaves), t, n, reinterpret_cast<uint8_t*>(scratch),
+                               reinterpret_cast<uint8_t*>(out), reinterpret_cast<hipStream_t>(stream)),
+            "launch_merkle_tree");
+}
+
 }  // namespace otedama

@@ -32,6 +32,7 @@ HIP_SOURCES = [
     "kernels/digest_batch.hip",
     "kernels/share_verify.hip",
     "kernels/channel_roots.hip",
+    "kernels/merkle_tree.hip",
     "runtime/gpu_miner.hip",
     "runtime/ops_launch.hip",
 ]
@@ -42,6 +43,7 @@ CXX_SOURCES = [
     "cpu/x11_cpu.cpp",
     "cpu/sv2_frame.cpp",
     "cpu/share_job.cpp",
+    "cpu/merkle_tree.cpp",
     "runtime/miner_common.cpp",
     "bindings.cpp",
 ]

@@ -38,7 +38,9 @@ def apply_config_file(fs: FlagSet, stderr: TextIO) -> None:
              ("retarget-seconds", ps.vardiff_retarget_seconds), ("journal", ps.journal_path),
              ("verify-device", ps.verify_device), ("verify-batch-ms", ps.verify_batch_ms),
              ("verify-batch-max", ps.verify_batch_max), ("verify-min-gpu", ps.verify_min_gpu),
-             ("job-device", ps.job_device), ("job-min-gpu", ps.job_min_gpu), ("http-addr", cfg.http_addr))
+             ("job-device", ps.job_device), ("job-min-gpu", ps.job_min_gpu),
+             ("template-file", ps.template_file), ("template-device", ps.template_device),
+             ("template-min-gpu", ps.template_min_gpu), ("http-addr", cfg.http_addr))
     default = type(ps)()
     for flag, value in pairs:
         unset_in_file = flag != "http-addr" and value == getattr(default, _FILE_FIELD[flag])
@@ -53,7 +55,9 @@ _FILE_FIELD = {"algorithms": "algorithm", "listen-sv2": "listen_sv2", "listen-v1
                "retarget-seconds": "vardiff_retarget_seconds", "journal": "journal_path",
                "verify-device": "verify_device", "verify-batch-ms": "verify_batch_ms",
                "verify-batch-max": "verify_batch_max", "verify-min-gpu": "verify_min_gpu",
-               "job-device": "job_device", "job-min-gpu": "job_min_gpu"}
+               "job-device": "job_device", "job-min-gpu": "job_min_gpu",
+               "template-file": "template_file", "template-device": "template_device",
+               "template-min-gpu": "template_min_gpu"}
 
 
 def verify_options(fs: FlagSet) -> dict:
@@ -89,6 +93,34 @@ def job_options_error(opts: dict) -> str | None:
     return None
 
 
+def template_options(fs: FlagSet) -> dict:
+    """The template tree's PoolOptions fields from the (file-filled) flags."""
+    return {"template_device": fs["template-device"], "template_min_gpu": fs["template-min-gpu"]}
+
+
+def template_options_error(opts: dict) -> str | None:
+    from otedama_amd.pool.devicepath import valid_device
+
+    if not valid_device(opts["template_device"]):
+        return f"--template-device {opts['template_device']!r} must be empty (off), cpu or cuda:N"
+    if opts["template_min_gpu"] < 0:
+        return "--template-min-gpu must not be negative (0 = the measured default)"
+    return None
+
+
+def template_source(fs: FlagSet):
+    """The pool's template source from the flags: a ``GbtFileSource`` over ``--template-file`` paying
+    ``--payout-address`` (OP_RETURN without one), or None for the synthetic chain."""
+    if not fs["template-file"]:
+        return None
+    from otedama_amd import btccrypto
+    from otedama_amd.pool.server import PoolOptions
+    from otedama_amd.pool.template import GbtFileSource
+
+    script = btccrypto.address_script_pubkey(fs["payout-address"]) if fs["payout-address"] else b"\x6a"
+    return GbtFileSource(fs["template-file"], script, fs.values.get("coinbase-message", PoolOptions.coinbase_message))
+
+
 def pool_flags(stderr: TextIO) -> FlagSet:
     fs = FlagSet("pool", stderr)
     fs.string("algorithms", "sha256d", "Comma-separated algorithms to serve (sha256d, scrypt, x11).")
@@ -115,6 +147,9 @@ def pool_flags(stderr: TextIO) -> FlagSet:
     fs.int("verify-min-gpu", 0, "Batches with fewer shares are hashed on the CPU (0 = the algorithm's measured default).")
     fs.string("job-device", "", "A job's SV2 standard-channel merkle roots in one call: cpu or cuda:N (empty = off).")
     fs.int("job-min-gpu", 0, "Fan-outs to fewer standard channels stay on the CPU (0 = the measured default).")
+    fs.string("template-file", "", "JSON file holding a getblocktemplate result, re-read for every block (empty = synthetic).")
+    fs.string("template-device", "", "A template's merkle trees in one call: cpu or cuda:N (empty = off, hashed in Python).")
+    fs.int("template-min-gpu", 0, "Templates of fewer leaves stay on the CPU (0 = the measured default).")
     fs.string("config", "", "Path to the YAML config file (default: $OTEDAMA_CONFIG or ~/.config/otedama/config.yaml).")
     return fs
 
@@ -137,7 +172,8 @@ def cmd_pool(args: list[str], stdout: TextIO, stderr: TextIO) -> int:
         if err:
             stderr.write(f"pool: payout address invalid: {err}\n")
             return EXIT_CONFIG
-    err = verify_options_error(verify_options(fs)) or job_options_error(job_options(fs))
+    err = verify_options_error(verify_options(fs)) or job_options_error(job_options(fs)) \
+        or template_options_error(template_options(fs))
     if err:
         stderr.write(f"pool: {err}\n")
         return EXIT_CONFIG
@@ -180,13 +216,14 @@ async def _serve(fs, algos: list[str], stdout: TextIO) -> int:
                            journal_path=journal or ":memory:", payout_scheme=fs["payout-scheme"],
                            dialect=fs["dialect"], noise=fs["sv2-noise"], noise_suite=fs["noise-suite"],
                            coinbase_message=fs.values.get("coinbase-message", PoolOptions.coinbase_message),
-                           noise_authority_secret=int(fs["noise-authority-key"] or "0", 16), **verify_options(fs), **job_options(fs))
+                           noise_authority_secret=int(fs["noise-authority-key"] or "0", 16), **verify_options(fs), **job_options(fs),
+                           **template_options(fs))
 
         def log(level, msg):
             stdout.write(f"[{level}] {msg}\n")
             stdout.flush()
 
-        p = PoolServer(opts, reg, log)
+        p = PoolServer(opts, reg, log, template_source=template_source(fs))
         await p.start()
         pools.append(p)
     srv = None

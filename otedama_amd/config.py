@@ -102,6 +102,10 @@ class PoolServerConfig:
     # a job's SV2 standard-channel merkle roots in one call (pool/jobroots.py); "" = off
     job_device: str = ""                # "", "cpu" or "cuda:N"
     job_min_gpu: int = 0                # fan-outs to fewer channels are computed on the CPU; 0 = the measured default
+    # real block templates (pool/template.py GbtFileSource) and their merkle trees (pool/templatetree.py)
+    template_file: str = ""             # JSON file holding a getblocktemplate result; "" = synthetic templates
+    template_device: str = ""           # "", "cpu" or "cuda:N"; "" = the branches are hashed in Python
+    template_min_gpu: int = 0           # templates of fewer leaves are computed on the CPU; 0 = the measured default
 
 
 @dataclass
@@ -199,6 +203,10 @@ class Config:
             issues.append(f"pool_server.job_device {ps.job_device!r} is not one of \"\", cpu, cuda:N")
         if ps.job_min_gpu < 0:
             issues.append("pool_server.job_min_gpu must be >= 0 (0 = the measured default)")
+        if not valid_device(str(ps.template_device)):
+            issues.append(f"pool_server.template_device {ps.template_device!r} is not one of \"\", cpu, cuda:N")
+        if ps.template_min_gpu < 0:
+            issues.append("pool_server.template_min_gpu must be >= 0 (0 = the measured default)")
         if issues:
             raise ConfigError("config validation failed:\n  - " + "\n  - ".join(issues))
 

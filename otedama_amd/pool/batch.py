@@ -127,3 +127,38 @@ def channel_roots(job: ShareJob, prefixes: Sequence[bytes], device=None) -> list
             if prepared is not None:  # as above
                 return op.roots(prepared, prefixes)
     return [root_of(job, p) for p in prefixes]
+
+
+def template_tree(txids: Sequence[bytes], wtxids: Sequence[bytes] = (), device=None):
+    """The two trees of a block template: ``(branches, witness_root)``. ``branches`` is ``merkle_branches(txids)``,
+    the coinbase's path through the txid tree; ``witness_root`` is ``merkle_root_full([bytes(32)] + wtxids)``, the
+    root of the wtxid tree with the coinbase's wtxid zeroed (BIP141), or ``None`` without wtxids. Both trees get 32
+    zero bytes as leaf 0: the path never depends on it. ``device=None``: those Python functions. ``"cpu"``: the
+    native ``merkle_tree_cpu``. ``"cuda:N"``: one ``ops.merkle.MerkleTree.tree`` round trip on that GPU, both trees
+    in it. A template over the op's limit of 262144 leaves is computed in Python whatever the device."""
+    from otedama_amd.ops.merkle_rows import MAX_LEAVES, pack_leaves, unpack_rows
+    from otedama_amd.pool.template import merkle_branches, merkle_root_full
+
+    txids, wtxids = list(map(bytes, txids)), list(map(bytes, wtxids))
+    if wtxids and len(wtxids) != len(txids):
+        raise ValueError(f"{len(wtxids)} wtxids for {len(txids)} txids")
+    for name, ids in (("txid", txids), ("wtxid", wtxids)):
+        if ids and set(map(len, ids)) != {32}:
+            raise ValueError(f"every {name} must be 32 bytes")
+    if device is not None and 1 + len(txids) <= MAX_LEAVES:
+        trees = [[bytes(32)] + txids] + ([[bytes(32)] + wtxids] if wtxids else [])
+        if str(device) == "cpu":
+            from otedama_amd.ops.native import require_native
+
+            packed, t, n = pack_leaves(trees)
+            out = unpack_rows(require_native().merkle_tree_cpu(packed, t, n), t, n)
+        else:
+            from otedama_amd.ops.merkle import MerkleTree  # imports torch
+
+            key = ("tree", "", str(device))
+            op = _ops.get(key)
+            if op is None:
+                op = _ops[key] = MerkleTree(device)
+            out = op.tree(trees)
+        return out[0][1], (out[1][0] if wtxids else None)
+    return merkle_branches(txids), (merkle_root_full([bytes(32)] + wtxids) if wtxids else None)

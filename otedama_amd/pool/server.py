@@ -89,6 +89,10 @@ class PoolOptions:
     # GPU (ops.roots.ChannelRoots.roots).
     job_device: str = ""
     job_min_gpu: int = 0           # a fan-out to fewer standard channels is computed on the CPU; 0 = the default
+    # A template's merkle trees (pool/templatetree.py). "" = off: the branches are hashed in Python, as before.
+    # "cpu": both trees in one native call per template. "cuda:N": in one call on that GPU (ops.merkle.MerkleTree).
+    template_device: str = ""
+    template_min_gpu: int = 0      # a template of fewer leaves is computed on the CPU; 0 = the default
 
 
 @dataclass
@@ -148,12 +152,17 @@ class _Worker:
 
 
 class PoolServer:
-    def __init__(self, opts: PoolOptions | None = None, registry: Registry | None = None, log=None):
+    def __init__(self, opts: PoolOptions | None = None, registry: Registry | None = None, log=None,
+                 template_source=None):
+        """``template_source``: any object with ``next_block() -> BlockTemplate`` and, optionally,
+        ``submit_block(raw: bytes, template)`` for a found block (``pool.template.GbtFileSource``); None = the
+        synthetic ``TemplateSource``."""
         self.opts = opts or PoolOptions()
         self.algo = algorithms.get(self.opts.algorithm)
         self.log = log or (lambda level, msg: None)
-        self.templates = TemplateSource(self.opts.payout_address, nbits=self.opts.nbits, n_txs=self.opts.n_txs,
-                                        coinbase_message=self.opts.coinbase_message)
+        self.templates = template_source or TemplateSource(
+            self.opts.payout_address, nbits=self.opts.nbits, n_txs=self.opts.n_txs,
+            coinbase_message=self.opts.coinbase_message)
         self.vardiff = Vardiff(VardiffConfig(target_share_seconds=self.opts.target_share_seconds,
                                              retarget_seconds=self.opts.retarget_seconds,
                                              min_difficulty=self.opts.min_difficulty),
@@ -211,6 +220,10 @@ class PoolServer:
         # device path (tests inject one; None = ChannelRoots.roots on opts.job_device)
         self._job_roots = None
         self.job_roots_fn = None
+        # the template's trees, made by the first new_block when opts.template_device is set; `template_tree_fn`
+        # replaces its device path (tests inject one; None = MerkleTree.tree on opts.template_device)
+        self._template_tree = None
+        self.template_tree_fn = None
         self._branches_of: BlockTemplate | None = None  # the block whose merkle branches are cached below
         self._branches: list[bytes] = []
         self._init_metrics(registry)
@@ -272,6 +285,8 @@ class PoolServer:
             await self._batcher.close()  # pending submits are answered (on the CPU) before the journal closes
         if self._job_roots is not None:
             self._job_roots.close()
+        if self._template_tree is not None:
+            self._template_tree.close()
         self._hash_pool.shutdown(wait=False, cancel_futures=True)
         self.journal.close()
 
@@ -318,6 +333,12 @@ class PoolServer:
     # ------------------------------------------------------------ jobs
     def new_block(self) -> PoolJob:
         self.block = self.templates.next_block()
+        if self.opts.template_device:  # both trees in one call, before the first coinbase_parts needs the commitment
+            if self._template_tree is None:
+                from otedama_amd.pool.templatetree import TemplateTree
+
+                self._template_tree = TemplateTree(self, device_tree=self.template_tree_fn)
+            self.block.set_tree(*self._template_tree.compute(self.block.txids, self.block.wtxids))
         self.jobs.clear()
         self._seen.clear()
         job = self._make_job(clean=True)
@@ -396,7 +417,7 @@ class PoolServer:
         if isinstance(pre, Verdict):
             return pre
         job, key, hdr = pre
-        return self._finish(worker, job_id, job, key, self.algo.hash(hdr))
+        return self._finish(worker, job_id, job, key, self.algo.hash(hdr), extranonce)
 
     async def validate_async(self, worker: _Worker, job_id: str, extranonce: bytes, ntime: int, nonce: int,
                              version: int) -> Verdict:
@@ -418,7 +439,7 @@ class PoolServer:
                 h = self.algo.hash(hdr)  # ~1 us: cheaper inline than a thread hop
             else:
                 h = await asyncio.get_running_loop().run_in_executor(self._hash_pool, self._slow_hash, hdr)
-            v = self._finish(worker, job_id, job, key, h)
+            v = self._finish(worker, job_id, job, key, h, extranonce)
         ms = (time.perf_counter() - t0) * 1e3
         self._validate_ms.append(ms)
         self._validate_log.append((time.monotonic(), ms))
@@ -492,7 +513,7 @@ class PoolServer:
                 out.append(self._reject(worker, job_id, job))
             else:
                 hdr, h = hashed[i]
-                out.append(self._finish(worker, job_id, job, hdr, h))
+                out.append(self._finish(worker, job_id, job, hdr, h, item[2]))
         return out
 
     def _get_batcher(self):
@@ -532,7 +553,10 @@ class PoolServer:
             return self._reject(worker, job_id, "duplicate-share")
         return job, hdr, hdr
 
-    def _finish(self, worker: _Worker, job_id: str, job: PoolJob, key: tuple, h: bytes) -> Verdict:
+    def _finish(self, worker: _Worker, job_id: str, job: PoolJob, key: tuple, h: bytes,
+                extranonce: bytes | None = None) -> Verdict:
+        """``key``: the share's 80-byte header. ``extranonce``: the share's, for the block a network-target share
+        makes; it decides no verdict."""
         # re-checked after the (possibly off-loop) hash: a new block or an identical concurrent submit
         if job.block is not self.block:
             return self._reject(worker, job_id, "stale-job")
@@ -569,8 +593,24 @@ class PoolServer:
                                             self.opts.payout_scheme)
             self.log("info", f"pool[{self.algo.name}]: BLOCK FOUND height={job.block.height} by {worker.name} "
                              f"payouts={json.dumps(pay)}")
+            self._submit_block(job, key, extranonce)
             asyncio.get_event_loop().call_soon(self.new_block)
         return Verdict(True, "", diff, h, is_block)
+
+    def _submit_block(self, job: PoolJob, header: bytes, extranonce: bytes | None) -> None:
+        """Serialise the found block and hand it to the template source, if that takes blocks. Whatever goes wrong
+        here is logged: the share's verdict and the journal's block row stand."""
+        submit = getattr(self.templates, "submit_block", None)
+        if submit is None or extranonce is None:
+            return
+        try:
+            from otedama_amd.pool.template import serialize_block
+
+            where = submit(serialize_block(bytes(header), job.coinb1 + extranonce + job.coinb2, job.block), job.block)
+            self.log("info", f"pool[{self.algo.name}]: block height={job.block.height} submitted"
+                             + (f" ({where})" if where else ""))
+        except Exception as exc:  # noqa: BLE001 - a block is too rare to lose the process over its submission
+            self.log("error", f"pool[{self.algo.name}]: submitting block height={job.block.height} failed ({exc!r})")
 
     def _credited(self, hdr: bytes) -> bool:
         """Duplicates are keyed on the full header across every live job of the block (see _precheck)."""
@@ -670,6 +710,14 @@ class PoolServer:
         return {"device": self.opts.job_device, "enabled": False, "fanouts": 0, "gpu_channels": 0, "cpu_channels": 0,
                 "last_channels": 0, "last_ms": 0.0, "device_errors": 0}
 
+    def template_stats(self) -> dict:
+        """The ``template`` object of /api/v1/pool: the template tree's device, whether the configured path is in
+        use (False when the feature is off, and after a device error has turned a GPU path off), and its counters."""
+        if self._template_tree is not None:
+            return self._template_tree.stats()
+        return {"device": self.opts.template_device, "enabled": False, "trees": 0, "gpu_leaves": 0, "cpu_leaves": 0,
+                "last_leaves": 0, "last_ms": 0.0, "device_errors": 0}
+
     def stats(self) -> dict:
         now = time.monotonic()
         live = self._live_workers()
@@ -685,6 +733,7 @@ class PoolServer:
             "fixed_difficulty": self.opts.fixed_difficulty,
             "verify": self.verify_stats(),
             "jobs": self.jobs_stats(),
+            "template": self.template_stats(),
             "new_block_at": list(self.new_block_at)[-64:],
             # per live connection: the difficulty in force, how often vardiff moved it, and when it last moved
             # (seconds after the channel opened: the time vardiff took to reach the difficulty it holds)

@@ -37,6 +37,14 @@ sj="$OUT/share_job_check"
   "$ROOT/tools/sanitize/share_job_check.cpp" -o "$sj" -lcrypto
 echo "== share job block: $sj"
 ASAN_OPTIONS="detect_leaks=1 abort_on_error=0" UBSAN_OPTIONS="print_stacktrace=1" "$sj" || { echo "share_job_check failed"; exit 1; }
+# The template tree's CPU twin (csrc/cpu/merkle_tree.cpp) under ASan + UBSan: exactly sized buffers over the chunk
+# edges, the roots against a fold written out in the check. A stand-alone program, host code only.
+mt="$OUT/merkle_tree_check"
+# shellcheck disable=SC2086
+"$CXX" "${FLAGS[@]}" ${SAN[asan]} "$ROOT/csrc/cpu/sha256_cpu.cpp" "$ROOT/csrc/cpu/merkle_tree.cpp" \
+  "$ROOT/tools/sanitize/merkle_tree_check.cpp" -o "$mt" -lcrypto
+echo "== template tree: $mt"
+ASAN_OPTIONS="detect_leaks=1 abort_on_error=0" UBSAN_OPTIONS="print_stacktrace=1" "$mt" || { echo "merkle_tree_check failed"; exit 1; }
 # libFuzzer (ASan + UBSan) over the SV2 frame scanner and the CPU hash paths.
 fz="$OUT/fuzz_native"
 "$CXX" -std=c++17 -O1 -g -march=x86-64-v2 "-I$ROOT/csrc/include" -fsanitize=fuzzer,address,undefined \
