@@ -133,6 +133,9 @@ py::dict stats_to_dict(const MinerStats& s) {
   d["clock_calib_rtt_us"] = s.clock_calib_rtt_us;
   d["clock_samples"] = s.clock_samples;
   d["host_abort"] = s.host_abort;
+  d["search_streams"] = s.search_streams;
+  d["scrypt_halves"] = s.scrypt_halves;
+  d["x11_overlap"] = s.x11_overlap;
   d["hashes_done_at_s"] = s.hashes_done_at_s;
   {
     py::dict ph;
@@ -438,6 +441,17 @@ PYBIND11_MODULE(_native, m) {
   m.def("gpu_arch_name", &gpu_arch_name);
   m.def("gpu_cu_count", &gpu_cu_count);
   m.def("scrypt_scratch_bytes", &scrypt_scratch_bytes);
+  // test hooks: what the launch files read from the environment (they launch nothing)
+  m.def("x11_midstage_polls", [] { return x11k::x11_midstage_polls(); });
+  m.def("_scrypt_romix_mode", [] {
+    bool write_polls = false;
+    uint32_t segments = 0;
+    scrypt_romix_mode(&write_polls, &segments);
+    py::dict d;
+    d["write_polls"] = write_polls;
+    d["segments"] = segments;
+    return d;
+  });
   // test hook: the /proc/self/maps check behind the CPU-stored abort word (GpuMiner host_abort)
   m.def("maps_range_writable", [](const std::string& maps, uint64_t lo, uint64_t hi) {
     return maps_range_writable(maps, uintptr_t(lo), uintptr_t(hi));

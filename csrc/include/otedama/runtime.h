@@ -113,6 +113,10 @@ struct MinerStats {
   uint64_t clock_samples = 0;         // per-launch clock stamps folded into the device -> host clock mapping
   bool host_abort = false;            // the abort word is stored by the CPU through the BAR (no control stream)
   uint64_t reserved_cus = 0;          // CUs left out of the search streams' CU mask (OTEDAMA_RESERVE_CUS)
+  // The GPU miner's buffer and stream layout as its device thread set it up (0 / false before that and on the CPU):
+  uint64_t search_streams = 0;        // 2: one stream per slot; 1: the slots share one (OTEDAMA_SEARCH_STREAMS=1)
+  bool scrypt_halves = false;         // each slot owns half the scrypt pad and grid (OTEDAMA_SCRYPT_HALVES=0: one pad)
+  bool x11_overlap = false;           // each slot owns an X11 digest plane set (OTEDAMA_X11_OVERLAP=0: one set)
   // Device-timeline time (s, from the miner's start) at which the batches counted in `hashes` had completed: a
   // rate over two samples, (hashes1 - hashes0) / (done_at1 - done_at0), is exact instead of quantized by launches.
   double hashes_done_at_s = 0;

@@ -15,6 +15,15 @@ namespace otedama {
 // Scratchpad bytes for `grid` ROMix blocks of 256 lane slots at lookup gap `gap` (scrypt_search.hip).
 uint64_t scrypt_scratch_bytes(int grid, int gap);
 
+// What the launch files read from the environment, for tests of those modes (read-only; nothing is launched).
+// scrypt_search.hip: whether the one-launch cooperative ROMix polls the abort word inside its write loop
+// (OTEDAMA_SCRYPT_POLL, read once per process) and the segment count of this moment (OTEDAMA_SCRYPT_SEGMENTS, read
+// at every launch; 0 = one launch).
+void scrypt_romix_mode(bool* write_polls, uint32_t* segments);
+namespace x11k {
+bool x11_midstage_polls();  // x11_stages_b.hip: OTEDAMA_X11_MIDPOLL, read once per process
+}
+
 // Device queries (gpu_miner.hip): 0 / "" when the runtime cannot answer.
 int gpu_device_count();
 std::string gpu_arch_name(int device);

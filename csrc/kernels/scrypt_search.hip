@@ -485,6 +485,11 @@ static uint32_t scrypt_segments() {
   return uint32_t(x < 1 ? 1 : (x > 64 ? 64 : x));
 }
 
+void scrypt_romix_mode(bool* write_polls, uint32_t* segments) {
+  *write_polls = scrypt_write_polls();
+  *segments = scrypt_segments();
+}
+
 // OTEDAMA_SCRYPT_SEG_GRID caps the segmented kernel's launch grid: "resident" = the chip's resident blocks (8 per CU
 // at 8 waves/SIMD), N = N blocks; each lane slot then walks several hashes per segment. Unset: the allocation grid
 // (one hash per lane slot).

@@ -325,6 +325,7 @@ struct GpuMiner::Run {
     }
     std::lock_guard<std::mutex> g(m.stats_mu_);
     m.stats_.reserved_cus = uint64_t(mask.reserved);
+    m.stats_.search_streams = one_stream ? 1 : kInflight;
   }
 
   // The abort word must never wait behind a search kernel. The CPU stores it itself when it can map the word
@@ -408,6 +409,9 @@ struct GpuMiner::Run {
     grid_v = cus * 64;
     // Two-chain kernel (4 waves/SIMD build): 128 blocks of 256 per CU (profiles/r2/sha_v2).
     grid_v2 = cus * 128;
+    std::lock_guard<std::mutex> g(m.stats_mu_);
+    m.stats_.scrypt_halves = scrypt_halves;
+    m.stats_.x11_overlap = x11_overlap;
   }
 
   // Start-up: probes bracketed by the launch and the stream sync on an idle device; the tightest bracket wins.

@@ -32,198 +32,18 @@ Sensitivity, checked once on scratch builds of gpu_miner.hip / launch_plan.h (ho
     ``count + 1`` instead of ``count`` on a group's last launch changes nothing: the offset is reset to 0 there.)
   * launch_scrypt gives both slots the X buffer of slot 0: the scrypt case fails (216 reference hits lost, none extra).
 """
-import hashlib
-import struct
 import time
 
 import pytest
 
+from miner_exact_cases import (NONCES, QUEUE_CAP, _assert_both_slots, _job, _key, _native, _pause, _wait, assert_exact,
+                               check_shares, reference_hits, region_hashes, searched_region)
+
 pytestmark = pytest.mark.gpu
-
-DEADLINE_S = 40.0  # every wait; a miss fails the test with the stats in its message
-NONCES = 1 << 32
-QUEUE_CAP = 1 << 20
-
-
-def _native():
-    from otedama_amd.ops.native import require_native
-
-    return require_native()
-
-
-def _header(seed: str) -> bytes:
-    body = hashlib.sha256(seed.encode()).digest() * 3
-    return struct.pack("<I", 0x20000000) + body[:72] + bytes(4)
-
-
-def _job(seed, target_int, epoch, job_id, algo="sha256d", **kw):
-    from otedama_amd.models.header import int_to_hash
-
-    return dict({"header": _header(seed), "target": int_to_hash(target_int), "epoch": epoch, "job_id": job_id,
-                 "algo": algo}, **kw)
 
 
 def _bswap(x: int) -> int:
     return int.from_bytes(x.to_bytes(4, "little"), "big")
-
-
-def _wait(m, pred, what):
-    end = time.monotonic() + DEADLINE_S
-    while True:
-        st = m.stats()
-        if st["faulted"]:
-            pytest.fail(f"{what}: the miner faulted: {st}")
-        if pred(st):
-            return st
-        if time.monotonic() > end:
-            pytest.fail(f"{what}: not reached within {DEADLINE_S} s: {st}")
-        time.sleep(0.001)
-
-
-def _pause(m):
-    """Pause and wait until the loop itself reports the batches in flight finished and their hits handed on."""
-    m.set_job(None)
-    return _wait(m, lambda st: st["idle"] and st["candidates"] == st["shares"] + st["rejected_candidates"], "pause")
-
-
-def _key(s):
-    return (s["version"], s["ntime"], s["extranonce2"], s["nonce"])
-
-
-# ---------------------------------------------------------------------------------------------- the searched region
-
-def searched_region(job, stats, sha_variants):
-    """Per stripe group the miner has searched: (kind, [(header80, version, ntime, extranonce2)], window). The groups
-    before stripe position cursor_k in full, then [0, cursor_nonce_off) of the group at cursor_k. kind "v" (version-
-    parallel: the window counts W3, the nonces are bswap(W3)), "k", "single", "scrypt" or "x11" (the nonce itself)."""
-    N = _native()
-    algo = job.get("algo", "sha256d")
-    start, stride = job.get("variant_start", 0), job.get("variant_stride", 1)
-    space = N.variant_space(job)
-    widest = N._launch_plan_rules(sha_variants=sha_variants, run=128)["layout"][0] if algo == "sha256d" else 1
-    groups, k = [], 0
-    while k < stats["cursor_k"] or (k == stats["cursor_k"] and stats["cursor_nonce_off"] > 0):
-        assert start + k * stride < space, (k, stats)  # the cursor never passes the end of the stripe by a group
-        run = [N.variant_header(job, start + k * stride)]
-        while len(run) < widest and start + (k + len(run)) * stride < space:
-            nxt = N.variant_header(job, start + (k + len(run)) * stride)
-            if nxt[0][64:76] != run[0][0][64:76]:
-                break
-            run.append(nxt)
-        nvar, use_v = (N._launch_plan_rules(sha_variants=sha_variants, run=len(run))["layout"] if algo == "sha256d"
-                       else (1, False))
-        kind = algo if algo != "sha256d" else "v" if use_v else "k" if nvar > 1 else "single"
-        groups.append((kind, run[:nvar], NONCES if k < stats["cursor_k"] else stats["cursor_nonce_off"]))
-        k += nvar
-    assert k == stats["cursor_k"] or (k > stats["cursor_k"] and groups[-1][2] < NONCES), (k, stats)  # a group boundary
-    return groups
-
-
-def region_hashes(region):
-    return sum(len(variants) * window for _, variants, window in region)
-
-
-def _digest(algo, h80):
-    if algo == "scrypt":
-        return hashlib.scrypt(h80, salt=h80, n=1024, r=1, p=1, dklen=32)
-    if algo == "x11":
-        return _native().x11(h80)
-    return hashlib.sha256(hashlib.sha256(h80).digest()).digest()
-
-
-def _chunk(window, per_position, target_int, cap):
-    """Positions per reference launch: the kernels pass a hash whose top word is <= the target's, so at most
-    cap / 8 expected candidates per launch (every launch's count is still asserted against cap)."""
-    p = ((target_int >> 224) + 1) / 2.0 ** 32
-    c = NONCES
-    while c > 1 and c * per_position * p > cap / 8:
-        c >>= 1
-    return min(c, window) if window else c
-
-
-def reference_hits(region, target_int):
-    """{(version, ntime, extranonce2, nonce)} of the region: candidates from the ops-API search kernels, each kept only
-    if its host digest passes the full 256-bit compare."""
-    import torch
-
-    from otedama_amd.models.header import int_to_hash
-    from otedama_amd.ops.search import ScryptSearch, Sha256dSearch, Sha256dSearchV, X11Search
-
-    tgt = int_to_hash(target_int)
-    cap = 1 << 14
-    made = {}
-
-    def searcher(kind):
-        if kind not in made:
-            made[kind] = (Sha256dSearchV("cuda:0", cap=cap, chains=1, occupancy8=False) if kind == "v"
-                          else ScryptSearch("cuda:0", cap=cap, grid=1024) if kind == "scrypt"
-                          else X11Search("cuda:0", cap=cap) if kind == "x11"
-                          else Sha256dSearch("cuda:0", cap=cap))
-        return made[kind]
-
-    cands, s = [], None  # (algo, header80, version, ntime, extranonce2, nonce)
-    for kind, variants, window in region:
-        s = searcher(kind)
-        if kind == "v":
-            assert len(variants) % 64 == 0
-            for lo in range(0, len(variants), 64):
-                part = variants[lo:lo + 64]
-                prep = s.prepare([v[0] for v in part], tgt)
-                step = _chunk(window, 64, target_int, cap)
-                for base in range(0, window, step):
-                    r = s.launch(prep, base, min(step, window - base))
-                    torch.cuda.synchronize()
-                    assert r.count() <= cap, r.count()
-                    cands += [("sha256d",) + part[vi] + (nonce,) for nonce, vi in r.hits()]
-            continue
-        algo = kind if kind in ("scrypt", "x11") else "sha256d"
-        for v in variants:
-            params = s.prepare(v[0], tgt)
-            step = _chunk(window, 1, target_int, cap)
-            if algo != "sha256d":
-                step = min(step, s.batch)
-            for base in range(0, window, step):
-                r = s.launch(params, base, min(step, window - base))
-                torch.cuda.synchronize()
-                assert r.count() <= cap, r.count()
-                cands += [(algo,) + v + (nonce,) for nonce in r.nonces()]
-    del s
-    made.clear()
-    torch.cuda.empty_cache()  # the reference's scrypt pad (32 GiB) and digest planes do not outlive it
-    ref = set()
-    for algo, hdr, version, ntime, en2, nonce in cands:
-        d = _digest(algo, hdr[:76] + struct.pack("<I", nonce))
-        if int.from_bytes(d, "little") <= target_int:
-            ref.add((version, ntime, en2, nonce))
-    return ref
-
-
-def check_shares(job, shares, target_int):
-    """Re-hash every share on the host from its own fields (the jobs here have no coinbase: extranonce2 is 0)."""
-    hdr, algo = job["header"], job.get("algo", "sha256d")
-    for s in shares:
-        assert s["extranonce2"] == 0 and s["job_id"] == job["job_id"], s
-        h80 = (struct.pack("<I", s["version"]) + hdr[4:68] + struct.pack("<I", s["ntime"]) + hdr[72:76]
-               + struct.pack("<I", s["nonce"]))
-        d = _digest(algo, h80)
-        assert d == s["hash"] and int.from_bytes(d, "little") <= target_int, s
-
-
-def assert_exact(shares, ref, st, hashes=None, other_shares=0):
-    """The one assertion of every case: the polled shares are the reference set, each once, and the counters agree.
-    `hashes`: the size of the region, for a miner that ran this work only (no launch aborted); `other_shares`: shares
-    of the same miner that belong to other work."""
-    keys = [_key(s) for s in shares]
-    got = set(keys)
-    lost, extra = ref - got, got - ref  # got == ref, said so that a failure names a few keys instead of both sets
-    assert not lost and not extra, {"n_ref": len(ref), "n_lost": len(lost), "lost": sorted(lost)[:8],
-                                    "n_extra": len(extra), "extra": sorted(extra)[:8], "stats": st}
-    assert len(shares) == len(got) == st["shares"] - other_shares, (len(shares), len(got), other_shares, st)
-    assert st["ring_overflow"] == st["dropped"] == st["verify_dropped"] == 0, st
-    assert st["candidates"] == st["shares"] + st["rejected_candidates"], st
-    if hashes is not None:
-        assert st["aborted_launches"] == 0, st
-        assert st["hashes"] == hashes, (st["hashes"], hashes)
 
 
 def run_to_exhaustion(job, target_int, sha_variants, batch_nonces=1 << 30):
@@ -373,15 +193,6 @@ def _paused_run(job, target_int, min_launches):
     region = searched_region(job, st, 128)
     check_shares(job, shares, target_int)
     return shares, st, region, reference_hits(region, target_int)
-
-
-def _assert_both_slots(ref, st):
-    """Launch i covers nonces [i * launch_hashes, (i + 1) * launch_hashes) and the two slots take turns: the reference
-    alone must put hits into launches of either parity, so the buffers of both slots are held to it."""
-    by_parity = [0, 0]
-    for k in ref:
-        by_parity[(k[3] // st["launch_hashes"]) % 2] += 1
-    assert min(by_parity) >= 20, (by_parity, st)
 
 
 def test_scrypt_both_halves_pause_shares_equal_the_reference():

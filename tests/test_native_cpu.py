@@ -533,3 +533,24 @@ def test_maps_check_requires_read_write_permissions():
     assert not N.maps_range_writable(maps, 0x7F0000200100, 0x7F0000200200)  # read-only
     assert not N.maps_range_writable(maps, 0x7F00000FFFF0, 0x7F0000100010)  # straddles two lines
     assert not N.maps_range_writable("", 0x1000, 0x1100)
+
+
+def test_mode_accessors_exist_and_launch_nothing(monkeypatch):
+    """What the miner mode tests read as evidence that a mode was on: the launch files' environment switches and the
+    layout fields of stats(). Nothing here touches a device."""
+    from otedama_amd.ops.native import require_native
+
+    N = require_native()
+    assert type(N.x11_midstage_polls()) is bool
+    monkeypatch.delenv("OTEDAMA_SCRYPT_SEGMENTS", raising=False)
+    mode = N._scrypt_romix_mode()
+    assert set(mode) == {"write_polls", "segments"}
+    assert type(mode["write_polls"]) is bool and type(mode["segments"]) is int and mode["segments"] == 0
+    for given, want in (("32", 32), ("1", 1), ("0", 1), ("100", 64), ("", 0)):  # read at every call, clamped to 1..64
+        monkeypatch.setenv("OTEDAMA_SCRYPT_SEGMENTS", given)
+        assert N._scrypt_romix_mode()["segments"] == want, given
+    assert N._scrypt_romix_mode()["write_polls"] is mode["write_polls"]  # read once per process
+    st = N.CpuMiner(1).stats()  # never started; the GPU miner fills these in when its device thread sets up
+    assert type(st["search_streams"]) is int and st["search_streams"] == 0
+    assert st["scrypt_halves"] is False and st["x11_overlap"] is False
+    assert st["host_abort"] is False and st["reserved_cus"] == 0
