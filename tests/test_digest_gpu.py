@@ -108,7 +108,8 @@ def test_sha256d_digest_equals_hashlib(n):
 @pytest.mark.parametrize("n", [1, 7, 8, 9, 63, 64, 65, 257, 512, 513])
 def test_scrypt_digest_equals_hashlib(n):
     """grid=2 (512 slots per chunk): the octet and wave granularity of the cooperative ROMix, its count rounding,
-    and at 513 a batch that crosses a chunk boundary. The op exposes no lookup gap, so there is no second pass."""
+    and at 513 a batch that crosses a chunk boundary. The op always launches SCRYPT_COOP; the other ROMix kernels
+    are held to bytes through the native launcher in tests/test_scrypt_romix_bytes_gpu.py."""
     assert _op("scrypt").capacity == 512
     _check_prefix("scrypt", n)
 
