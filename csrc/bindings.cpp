@@ -648,6 +648,45 @@ PYBIND11_MODULE(_native, m) {
     py_launch_merkle_tree(leaves, t, n, scratch, out, stream);
   }, py::arg("leaves"), py::arg("t"), py::arg("n"), py::arg("scratch"), py::arg("out"), py::arg("stream") = 0);
 
+  // secp256k1 multiplication: n 128-byte rows -> n 48-byte rows (otedama/secp256k1.h).
+  m.def("secp256k1_mul_cpu", [](const py::buffer& rows) {
+    // bytes, a bytearray or a memoryview: a caller that packs into a bytearray can wipe its scalars afterwards
+    const py::buffer_info info = rows.request();
+    if (info.ndim != 1 || info.itemsize != 1 || (info.size && info.strides[0] != 1))
+      throw std::invalid_argument("rows: expected contiguous bytes");
+    const size_t size = size_t(info.size);
+    if (size == 0 || size % kSecpRowBytes || size / kSecpRowBytes > kSecpMaxRows)
+      throw std::invalid_argument("rows: expected 1..65536 rows of 128 bytes");
+    std::string rs(static_cast<const char*>(info.ptr), size);  // the caller's buffer may change once the GIL is gone
+    const uint32_t n = uint32_t(size / kSecpRowBytes);
+    std::string out(size_t(n) * kSecpOutBytes, '\0');
+    {
+      py::gil_scoped_release r;  // a flush of the pool's handshake batcher is thousands of ladders
+      secp256k1_mul_cpu(reinterpret_cast<const uint8_t*>(rs.data()), n, reinterpret_cast<uint8_t*>(&out[0]));
+    }
+    volatile char* wipe = &rs[0];  // the copy held the scalars
+    for (size_t i = 0; i < rs.size(); ++i) wipe[i] = 0;
+    return py::bytes(out);
+  }, py::arg("rows"));
+  m.def("ellswift_encode_native", [](const py::bytes& x32, const py::bytes& rand_bytes) -> py::object {
+    std::string x = need(x32, 32, "x32"), rnd = rand_bytes;
+    uint8_t out[64];
+    const int rc = ellswift_encode_cpu(reinterpret_cast<const uint8_t*>(x.data()),
+                                       reinterpret_cast<const uint8_t*>(rnd.data()), rnd.size(), out);
+    if (rc < 0) throw std::invalid_argument("ellswift: x is not on secp256k1");
+    if (rc == 0) return py::none();
+    return to_bytes(out, 64);
+  }, py::arg("x32"), py::arg("rand_bytes"));
+  m.attr("SECP_ROW_BYTES") = kSecpRowBytes;
+  m.attr("SECP_OUT_BYTES") = kSecpOutBytes;
+  m.attr("SECP_MAX_ROWS") = kSecpMaxRows;
+  m.def("launch_secp256k1_mul", [](uintptr_t rows, uint32_t n, uintptr_t out, uintptr_t stream) {
+    if (n == 0 || n > kSecpMaxRows) throw std::invalid_argument("need n in 1..65536");
+    if (rows == 0 || out == 0) throw std::invalid_argument("need rows, out != 0");
+    if ((rows | out) & 15u) throw std::invalid_argument("rows and out must be 16-byte aligned");
+    py_launch_secp256k1_mul(rows, n, out, stream);
+  }, py::arg("rows"), py::arg("n"), py::arg("out"), py::arg("stream") = 0);
+
   py::class_<MinerBase, std::shared_ptr<MinerBase>>(m, "Miner")
       .def("start", &MinerBase::start, py::call_guard<py::gil_scoped_release>())
       .def("stop", &MinerBase::stop, py::call_guard<py::gil_scoped_release>())

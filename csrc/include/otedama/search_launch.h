@@ -9,6 +9,7 @@
 #include "otedama/hitsink.h"
 #include "otedama/job.h"
 #include "otedama/merkle_tree.h"
+#include "otedama/secp256k1.h"
 
 namespace otedama {
 
@@ -77,6 +78,10 @@ void py_launch_channel_roots(uintptr_t job, uintptr_t prefixes, uint32_t n, uint
 void py_launch_merkle_tree(uintptr_t leaves, uint32_t t, uint32_t n, uintptr_t scratch, uintptr_t out,
                            uintptr_t stream);
 
+// secp256k1 multiplication (otd_secp256k1_mul of secp256k1_mul.hip; rows, limits and the CPU twin:
+// otedama/secp256k1.h): n 128-byte rows -> n 48-byte rows. Same conventions as above; both arrays are 16-byte aligned.
+void py_launch_secp256k1_mul(uintptr_t rows, uint32_t n, uintptr_t out, uintptr_t stream);
+
 }  // namespace otedama
 
 #ifdef __HIPCC__
@@ -127,6 +132,9 @@ hipError_t launch_channel_roots(const void* job, const uint8_t* prefixes, uint32
 // above kMerkleTreeMaxLeaves, a null or not 16-byte aligned leaves or out, and the same of scratch when n > 512.
 hipError_t launch_merkle_tree(const uint8_t* leaves, uint32_t t, uint32_t n, uint8_t* scratch, uint8_t* out,
                               hipStream_t s);
+// secp256k1 multiplication: hipErrorInvalidValue, before launching anything, for n == 0 or above kSecpMaxRows, and a
+// null or not 16-byte aligned rows or out.
+hipError_t launch_secp256k1_mul(const uint8_t* rows, uint32_t n, uint8_t* out, hipStream_t s);
 
 }  // namespace otedama
 #endif

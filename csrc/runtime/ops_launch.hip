@@ -120,4 +120,10 @@ void py_launch_merkle_tree(uintptr_t leaves, uint32_t t, uint32_t n, uintptr_t s
             "launch_merkle_tree");
 }
 
+void py_launch_secp256k1_mul(uintptr_t rows, uint32_t n, uintptr_t out, uintptr_t stream) {
+  hip_check(launch_secp256k1_mul(reinterpret_cast<const uint8_t*>(rows), n, reinterpret_cast<uint8_t*>(out),
+                                 reinterpret_cast<hipStream_t>(stream)),
+            "launch_secp256k1_mul");
+}
+
 }  // namespace otedama

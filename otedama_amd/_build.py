@@ -33,6 +33,7 @@ HIP_SOURCES = [
     "kernels/share_verify.hip",
     "kernels/channel_roots.hip",
     "kernels/merkle_tree.hip",
+    "kernels/secp256k1_mul.hip",
     "runtime/gpu_miner.hip",
     "runtime/ops_launch.hip",
 ]
@@ -44,6 +45,7 @@ CXX_SOURCES = [
     "cpu/sv2_frame.cpp",
     "cpu/share_job.cpp",
     "cpu/merkle_tree.cpp",
+    "cpu/secp256k1.cpp",
     "runtime/miner_common.cpp",
     "bindings.cpp",
 ]

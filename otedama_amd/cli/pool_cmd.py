@@ -40,7 +40,9 @@ def apply_config_file(fs: FlagSet, stderr: TextIO) -> None:
              ("verify-batch-max", ps.verify_batch_max), ("verify-min-gpu", ps.verify_min_gpu),
              ("job-device", ps.job_device), ("job-min-gpu", ps.job_min_gpu),
              ("template-file", ps.template_file), ("template-device", ps.template_device),
-             ("template-min-gpu", ps.template_min_gpu), ("http-addr", cfg.http_addr))
+             ("template-min-gpu", ps.template_min_gpu), ("handshake-device", ps.handshake_device),
+             ("handshake-batch-ms", ps.handshake_batch_ms), ("handshake-batch-max", ps.handshake_batch_max),
+             ("handshake-min-gpu", ps.handshake_min_gpu), ("http-addr", cfg.http_addr))
     default = type(ps)()
     for flag, value in pairs:
         unset_in_file = flag != "http-addr" and value == getattr(default, _FILE_FIELD[flag])
@@ -57,7 +59,9 @@ _FILE_FIELD = {"algorithms": "algorithm", "listen-sv2": "listen_sv2", "listen-v1
                "verify-batch-max": "verify_batch_max", "verify-min-gpu": "verify_min_gpu",
                "job-device": "job_device", "job-min-gpu": "job_min_gpu",
                "template-file": "template_file", "template-device": "template_device",
-               "template-min-gpu": "template_min_gpu"}
+               "template-min-gpu": "template_min_gpu", "handshake-device": "handshake_device",
+               "handshake-batch-ms": "handshake_batch_ms", "handshake-batch-max": "handshake_batch_max",
+               "handshake-min-gpu": "handshake_min_gpu"}
 
 
 def verify_options(fs: FlagSet) -> dict:
@@ -108,6 +112,24 @@ def template_options_error(opts: dict) -> str | None:
     return None
 
 
+def handshake_options(fs: FlagSet) -> dict:
+    """The handshake batcher's PoolOptions fields from the (file-filled) flags."""
+    return {"handshake_device": fs["handshake-device"], "handshake_batch_ms": fs["handshake-batch-ms"],
+            "handshake_batch_max": fs["handshake-batch-max"], "handshake_min_gpu": fs["handshake-min-gpu"]}
+
+
+def handshake_options_error(opts: dict) -> str | None:
+    from otedama_amd.pool.devicepath import valid_device
+
+    if not valid_device(opts["handshake_device"]):
+        return f"--handshake-device {opts['handshake_device']!r} must be empty (off), cpu or cuda:N"
+    if opts["handshake_batch_ms"] <= 0 or not 0 < opts["handshake_batch_max"] <= 21845:
+        return "--handshake-batch-ms must be positive and --handshake-batch-max in 1..21845"
+    if opts["handshake_min_gpu"] < 0:
+        return "--handshake-min-gpu must not be negative (0 = the measured default)"
+    return None
+
+
 def template_source(fs: FlagSet):
     """The pool's template source from the flags: a ``GbtFileSource`` over ``--template-file`` paying
     ``--payout-address`` (OP_RETURN without one), or None for the synthetic chain."""
@@ -150,6 +172,10 @@ def pool_flags(stderr: TextIO) -> FlagSet:
     fs.string("template-file", "", "JSON file holding a getblocktemplate result, re-read for every block (empty = synthetic).")
     fs.string("template-device", "", "A template's merkle trees in one call: cpu or cuda:N (empty = off, hashed in Python).")
     fs.int("template-min-gpu", 0, "Templates of fewer leaves stay on the CPU (0 = the measured default).")
+    fs.string("handshake-device", "", "With --sv2-noise, the handshakes' secp256k1 arithmetic in batches: cpu or cuda:N (empty = off).")
+    fs.float("handshake-batch-ms", 2.0, "Handshake batch flush delay after the oldest waiting handshake, in milliseconds.")
+    fs.int("handshake-batch-max", 4096, "Handshake batch flush size.")
+    fs.int("handshake-min-gpu", 0, "Batches of fewer handshakes are computed on the CPU (0 = the measured default).")
     fs.string("config", "", "Path to the YAML config file (default: $OTEDAMA_CONFIG or ~/.config/otedama/config.yaml).")
     return fs
 
@@ -173,7 +199,7 @@ def cmd_pool(args: list[str], stdout: TextIO, stderr: TextIO) -> int:
             stderr.write(f"pool: payout address invalid: {err}\n")
             return EXIT_CONFIG
     err = verify_options_error(verify_options(fs)) or job_options_error(job_options(fs)) \
-        or template_options_error(template_options(fs))
+        or template_options_error(template_options(fs)) or handshake_options_error(handshake_options(fs))
     if err:
         stderr.write(f"pool: {err}\n")
         return EXIT_CONFIG
@@ -217,7 +243,7 @@ async def _serve(fs, algos: list[str], stdout: TextIO) -> int:
                            dialect=fs["dialect"], noise=fs["sv2-noise"], noise_suite=fs["noise-suite"],
                            coinbase_message=fs.values.get("coinbase-message", PoolOptions.coinbase_message),
                            noise_authority_secret=int(fs["noise-authority-key"] or "0", 16), **verify_options(fs), **job_options(fs),
-                           **template_options(fs))
+                           **template_options(fs), **handshake_options(fs))
 
         def log(level, msg):
             stdout.write(f"[{level}] {msg}\n")

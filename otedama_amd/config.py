@@ -106,6 +106,11 @@ class PoolServerConfig:
     template_file: str = ""             # JSON file holding a getblocktemplate result; "" = synthetic templates
     template_device: str = ""           # "", "cpu" or "cuda:N"; "" = the branches are hashed in Python
     template_min_gpu: int = 0           # templates of fewer leaves are computed on the CPU; 0 = the measured default
+    # Noise handshakes in batches (pool/handshakes.py); "" = off
+    handshake_device: str = ""          # "", "cpu" or "cuda:N"
+    handshake_batch_ms: float = 2.0     # flush this long after the oldest waiting handshake
+    handshake_batch_max: int = 4096     # flush at this many waiting handshakes
+    handshake_min_gpu: int = 0          # fewer handshakes than this are computed on the CPU; 0 = the measured default
 
 
 @dataclass
@@ -207,6 +212,14 @@ class Config:
             issues.append(f"pool_server.template_device {ps.template_device!r} is not one of \"\", cpu, cuda:N")
         if ps.template_min_gpu < 0:
             issues.append("pool_server.template_min_gpu must be >= 0 (0 = the measured default)")
+        if not valid_device(str(ps.handshake_device)):
+            issues.append(f"pool_server.handshake_device {ps.handshake_device!r} is not one of \"\", cpu, cuda:N")
+        if ps.handshake_batch_ms <= 0:
+            issues.append("pool_server.handshake_batch_ms must be > 0")
+        if not 0 < ps.handshake_batch_max <= 21845:
+            issues.append("pool_server.handshake_batch_max must be in 1..21845 (three rows a handshake, 65536 a call)")
+        if ps.handshake_min_gpu < 0:
+            issues.append("pool_server.handshake_min_gpu must be >= 0 (0 = the measured default)")
         if issues:
             raise ConfigError("config validation failed:\n  - " + "\n  - ".join(issues))
 

@@ -93,6 +93,13 @@ class PoolOptions:
     # "cpu": both trees in one native call per template. "cuda:N": in one call on that GPU (ops.merkle.MerkleTree).
     template_device: str = ""
     template_min_gpu: int = 0      # a template of fewer leaves is computed on the CPU; 0 = the default
+    # Noise handshakes in batches (pool/handshakes.py), with `noise` on. "" = off: every handshake's secp256k1
+    # arithmetic runs in Python on the event loop, as before. "cpu": the multiplications of concurrent handshakes in
+    # one native call per batch on one worker thread. "cuda:N": on that GPU (ops.secp.Secp256k1Mul.mul).
+    handshake_device: str = ""
+    handshake_batch_ms: float = 2.0   # flush this long after the oldest waiting handshake
+    handshake_batch_max: int = 4096   # flush at this many waiting handshakes (three rows each)
+    handshake_min_gpu: int = 0        # a flush of fewer handshakes is computed on the CPU; 0 = the default
 
 
 @dataclass
@@ -200,6 +207,7 @@ class PoolServer:
 
             auth_priv, self.noise_authority_pub = noise.keypair(self.opts.noise_authority_secret or None)
             self._noise_static, static_pub = noise.keypair()
+            self._noise_static_x = (static_pub, 0)  # keypair() negates the secret where Y is odd
             now = int(time.time())
             self._noise_cert = noise.certificate_payload(static_pub, auth_priv, now - 3600,
                                                          now + self.opts.noise_cert_seconds)
@@ -224,6 +232,10 @@ class PoolServer:
         # replaces its device path (tests inject one; None = MerkleTree.tree on opts.template_device)
         self._template_tree = None
         self.template_tree_fn = None
+        # the handshake batcher, made by the first Noise connection when opts.handshake_device is set;
+        # `handshake_mul_fn` replaces its device path (tests inject one; None = Secp256k1Mul.mul on that device)
+        self._handshakes = None
+        self.handshake_mul_fn = None
         self._branches_of: BlockTemplate | None = None  # the block whose merkle branches are cached below
         self._branches: list[bytes] = []
         self._init_metrics(registry)
@@ -281,6 +293,8 @@ class PoolServer:
                 await asyncio.wait_for(s.wait_closed(), 2)
             except asyncio.TimeoutError:
                 pass
+        if self._handshakes is not None:
+            await self._handshakes.stop()  # waiting handshakes get their results (from the CPU)
         if self._batcher is not None:
             await self._batcher.close()  # pending submits are answered (on the CPU) before the journal closes
         if self._job_roots is not None:
@@ -718,6 +732,22 @@ class PoolServer:
         return {"device": self.opts.template_device, "enabled": False, "trees": 0, "gpu_leaves": 0, "cpu_leaves": 0,
                 "last_leaves": 0, "last_ms": 0.0, "device_errors": 0}
 
+    def handshake_stats(self) -> dict:
+        """The ``handshake`` object of /api/v1/pool: the handshake batcher's device, whether the configured path is
+        in use (False when the feature is off, and after a device error has turned a GPU path off), and its
+        counters."""
+        if self._handshakes is not None:
+            return self._handshakes.stats()
+        return {"device": self.opts.handshake_device, "enabled": False, "batches": 0, "gpu_handshakes": 0,
+                "cpu_handshakes": 0, "last_batch": 0, "max_batch": 0, "last_ms": 0.0, "device_errors": 0}
+
+    def _get_handshakes(self):
+        if self._handshakes is None:
+            from otedama_amd.pool.handshakes import HandshakeBatcher
+
+            self._handshakes = HandshakeBatcher(self, device_mul=self.handshake_mul_fn)
+        return self._handshakes
+
     def stats(self) -> dict:
         now = time.monotonic()
         live = self._live_workers()
@@ -734,6 +764,7 @@ class PoolServer:
             "verify": self.verify_stats(),
             "jobs": self.jobs_stats(),
             "template": self.template_stats(),
+            "handshake": self.handshake_stats(),
             "new_block_at": list(self.new_block_at)[-64:],
             # per live connection: the difficulty in force, how often vardiff moved it, and when it last moved
             # (seconds after the channel opened: the time vardiff took to reach the difficulty it holds)
@@ -764,8 +795,10 @@ class PoolServer:
             from otedama_amd.stratum import noise
 
             try:
-                reader, writer = await noise.server_handshake(reader, writer, self._noise_static, self._noise_cert,
-                                                              suite=self.opts.noise_suite or None)
+                reader, writer = await noise.server_handshake(
+                    reader, writer, self._noise_static, self._noise_cert, suite=self.opts.noise_suite or None,
+                    static_x=self._noise_static_x,
+                    ec_batcher=self._get_handshakes() if self.opts.handshake_device else None)
             except (noise.NoiseError, asyncio.IncompleteReadError, asyncio.TimeoutError, ConnectionError, OSError):
                 writer.close()
                 self.reject_reasons["noise-handshake"] = self.reject_reasons.get("noise-handshake", 0) + 1

@@ -147,8 +147,12 @@ def ecdh_x(priv: int, ell_theirs: bytes) -> bytes:
     return r[0].to_bytes(32, "big")
 
 
-def xdh(priv: int, ell_theirs: bytes, ell_ours: bytes, initiating: bool) -> bytes:
-    """BIP324 ``v2_ecdh``: both parties hash (initiator's encoding ‖ responder's encoding ‖ shared x)."""
-    x = ecdh_x(priv, ell_theirs)
+def xdh_from_x(x: bytes, ell_theirs: bytes, ell_ours: bytes, initiating: bool) -> bytes:
+    """The hash of :func:`xdh` for a shared x computed elsewhere (``ecdh_x``, or a batch of them on a device)."""
     a, b = (ell_ours, ell_theirs) if initiating else (ell_theirs, ell_ours)
     return _tagged("bip324_ellswift_xonly_ecdh", a + b + x)
+
+
+def xdh(priv: int, ell_theirs: bytes, ell_ours: bytes, initiating: bool) -> bytes:
+    """BIP324 ``v2_ecdh``: both parties hash (initiator's encoding ‖ responder's encoding ‖ shared x)."""
+    return xdh_from_x(ecdh_x(priv, ell_theirs), ell_theirs, ell_ours, initiating)

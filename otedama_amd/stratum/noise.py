@@ -24,7 +24,9 @@ skips ee/es and never authenticates the pool. This is the full NX pattern
 handshake hash, and an authenticated payload (e.g. a signed certificate).
 DH(k, P) = x-coordinate of k·P (32 bytes). ChaCha20-Poly1305 runs in the
 native extension (OpenSSL EVP); the EC arithmetic is host Python (one
-handshake per connection).
+handshake per connection), unless a pool hands the responder's three
+multiplications to a batch (``Responder.ec_requests`` / ``write_message2(ec=)``,
+pool/handshakes.py).
 """
 from __future__ import annotations
 
@@ -206,16 +208,27 @@ class Initiator:
 
 class Responder:
     """Pool side, holding the long-term static key. ``suite=None`` accepts either suite, chosen by the length of
-    message 1 (64 bytes: ElligatorSwift, 32: legacy); a fixed suite refuses the other."""
+    message 1 (64 bytes: ElligatorSwift, 32: legacy); a fixed suite refuses the other.
 
-    def __init__(self, static_priv: int, prologue: bytes = b"", suite: str | None = None):
+    ``static_x``: ``(x, y_parity)`` of ``static_priv``·G, 32 bytes and 0 or 1, when the caller has it already (a pool
+    computes it once per process, :func:`static_point`): the responder then multiplies three times per handshake,
+    not five. The bytes on the wire are the same either way.
+
+    The curve arithmetic can be done elsewhere, in batches (``pool/handshakes.py``): :meth:`ec_requests` names the
+    three products once message 1 is read and :meth:`write_message2` takes their results as ``ec=``."""
+
+    def __init__(self, static_priv: int, prologue: bytes = b"", suite: str | None = None,
+                 static_x: tuple[bytes, int] | None = None):
         self.suite = _suite(suite) if suite is not None else None
         self.prologue = prologue
         self.static_priv = static_priv
-        self.s_xonly = keypair(static_priv)[1]  # what pins and certificates name, in both suites
+        self.static_x = static_x
+        # what pins and certificates name, in both suites
+        self.s_xonly = static_x[0] if static_x is not None else keypair(static_priv)[1]
         self.send: CipherState | None = None
         self.recv: CipherState | None = None
         self.ss: SymmetricState | None = None
+        self.e: int | None = None
 
     def _dh(self, priv: int, theirs: bytes, ours: bytes) -> bytes:
         if self.suite == "ellswift":
@@ -230,20 +243,86 @@ class Responder:
         self.suite = by_len
         self.ss = SymmetricState(PROTOCOL_NAME_ELLSWIFT if by_len == "ellswift" else PROTOCOL_NAME)
         self.ss.mix_hash(self.prologue)
-        if by_len == "ellswift":
-            self.s, self.s_pub = _ell_keypair(self.static_priv)
-        else:
-            self.s, self.s_pub = keypair(self.static_priv)
+        if self.static_x is None:
+            if by_len == "ellswift":
+                self.s, self.s_pub = _ell_keypair(self.static_priv)
+            else:
+                self.s, self.s_pub = keypair(self.static_priv)
+        elif by_len == "ellswift":  # _ell_keypair: the secret as given, a fresh encoding of its x
+            self.s, self.s_pub = self.static_priv, self._encode(self.static_x[0])
+        else:                       # keypair: the secret negated where Y is odd, the x itself
+            self.s = ec.N - self.static_priv if self.static_x[1] else self.static_priv
+            self.s_pub = self.static_x[0]
         self.re = msg
         self.ss.mix_hash(msg)
         self.ss.mix_hash(b"")
 
-    def write_message2(self, payload: bytes = b"") -> bytes:
+    @staticmethod
+    def _encode(x: bytes) -> bytes:
+        """``ellswift.encode`` of a 32-byte x, by the native encoder where the extension is loaded, in Python
+        otherwise. Either way every try draws ``os.urandom(33)``, so the same random stream gives the same bytes."""
+        from otedama_amd.ops.native import load
+
+        native = load(build_if_missing=False)
+        if native is None:
+            return ellswift.encode(int.from_bytes(x, "big"))
+        while True:
+            enc = native.ellswift_encode_native(x, os.urandom(33))
+            if enc is not None:
+                return enc
+
+    def _mix_dh(self, x: bytes, ours: bytes) -> None:
+        """mix_key of one DH whose shared x is known: BIP324's tagged hash in the ellswift suite, the x itself in
+        the legacy one."""
+        self.ss.mix_key(ellswift.xdh_from_x(x, self.re, ours, initiating=False) if self.suite == "ellswift" else x)
+
+    def ec_requests(self) -> list[tuple]:
+        """After :meth:`read_message1`: the three ``(scalar, kind, point)`` rows of this handshake for
+        ``ops.secp_rows.pack_rows`` (e·G, e·X, s·X; X is message 1's key, kind 2 or 1 by suite). Draws the ephemeral
+        secret e, as :meth:`write_message2` would."""
+        from otedama_amd.ops.secp_rows import KIND_ELLSWIFT, KIND_G, KIND_XONLY
+
+        e = None
+        while e is None or not 0 < e < ec.N:
+            e = int.from_bytes(os.urandom(32), "big")
+        self.e = e
+        kind = KIND_ELLSWIFT if self.suite == "ellswift" else KIND_XONLY
+        return [(e, KIND_G, b""), (e, kind, self.re), (self.s, kind, self.re)]
+
+    def write_message2(self, payload: bytes = b"", ec: list[tuple] | None = None) -> bytes:
+        """``ec``: the ``(x, y_parity, status)`` results of :meth:`ec_requests`' rows, in order; None computes them
+        here, in Python. A nonzero status is a ``NoiseError``."""
+        if ec is None:
+            return self._write_message2_python(payload)
+        if self.e is None or len(ec) != 3:
+            raise NoiseError("noise: write_message2(ec=) needs the three results of ec_requests()")
+        if any(status for _x, _parity, status in ec):
+            raise NoiseError("noise: invalid secp256k1 public key")
+        (ex, _ep, _), (ee, _, _), (es, _, _) = ec
+        # the legacy key is x-only with Y even: a secret whose Y is odd is negated, which leaves every x as it is
+        e_pub = self._encode(ex) if self.suite == "ellswift" else ex
+        self.e = None
+        return self._finish_message2(payload, e_pub, ee, es)
+
+    def _write_message2_python(self, payload: bytes) -> bytes:
         e, e_pub = _ell_keypair() if self.suite == "ellswift" else keypair()
+        # message 1's key is decoded and lifted once, for both DHs
+        if self.suite == "ellswift":
+            pt = ec.lift_x(ellswift.decode(self.re))
+        else:
+            pt = ec.lift_x(int.from_bytes(self.re, "big"))
+        if pt is None:
+            raise NoiseError("noise: invalid secp256k1 public key")
+        ee, es = ec.point_mul(pt, e), ec.point_mul(pt, self.s)
+        if ee is None or es is None:
+            raise NoiseError("noise: DH produced the point at infinity")
+        return self._finish_message2(payload, e_pub, ee[0].to_bytes(32, "big"), es[0].to_bytes(32, "big"))
+
+    def _finish_message2(self, payload: bytes, e_pub: bytes, ee: bytes, es: bytes) -> bytes:
         self.ss.mix_hash(e_pub)
-        self.ss.mix_key(self._dh(e, self.re, e_pub))           # ee
+        self._mix_dh(ee, e_pub)                                # ee
         enc_s = self.ss.encrypt_and_hash(self.s_pub)
-        self.ss.mix_key(self._dh(self.s, self.re, self.s_pub))  # es
+        self._mix_dh(es, self.s_pub)                           # es
         enc_p = self.ss.encrypt_and_hash(payload)
         r, i = self.ss.split()
         self.send, self.recv = i, r               # responder sends with k2, receives with k1
@@ -252,6 +331,12 @@ class Responder:
     @property
     def handshake_hash(self) -> bytes:
         return self.ss.h
+
+
+def static_point(static_priv: int) -> tuple[bytes, int]:
+    """``(x, y_parity)`` of ``static_priv``·G for :class:`Responder`'s ``static_x``."""
+    x, y = ec.point_mul(ec.G, static_priv)
+    return x.to_bytes(32, "big"), y & 1
 
 
 # ------------------------------------------------------------------ framing
@@ -337,11 +422,18 @@ async def client_handshake(reader, writer, expected_static: bytes | None = None,
 
 
 async def server_handshake(reader, writer, static_priv: int, payload: bytes = b"", timeout: float = 10.0,
-                           suite: str | None = None):
-    """Runs NX as responder (either suite unless ``suite`` fixes one); returns (EncryptedReader, EncryptedWriter)."""
-    hs = Responder(static_priv, suite=suite)
+                           suite: str | None = None, static_x: tuple[bytes, int] | None = None, ec_batcher=None):
+    """Runs NX as responder (either suite unless ``suite`` fixes one); returns (EncryptedReader, EncryptedWriter).
+    ``ec_batcher``: an object whose ``await submit(rows)`` answers :meth:`Responder.ec_requests`' rows
+    (``pool.handshakes.HandshakeBatcher``); the wait for it counts towards ``timeout``."""
+    hs = Responder(static_priv, suite=suite, static_x=static_x)
+    deadline = asyncio.get_running_loop().time() + timeout
     hs.read_message1(await asyncio.wait_for(_read_hs(reader), timeout))
-    m2 = hs.write_message2(payload)
+    if ec_batcher is None:
+        m2 = hs.write_message2(payload)
+    else:
+        left = max(deadline - asyncio.get_running_loop().time(), 0.0)
+        m2 = hs.write_message2(payload, ec=await asyncio.wait_for(ec_batcher.submit(hs.ec_requests()), left))
     writer.write(struct.pack("<H", len(m2)) + m2)
     await writer.drain()
     return EncryptedReader(reader, hs.recv), EncryptedWriter(writer, hs.send)

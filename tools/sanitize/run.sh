@@ -45,6 +45,14 @@ mt="$OUT/merkle_tree_check"
   "$ROOT/tools/sanitize/merkle_tree_check.cpp" -o "$mt" -lcrypto
 echo "== template tree: $mt"
 ASAN_OPTIONS="detect_leaks=1 abort_on_error=0" UBSAN_OPTIONS="print_stacktrace=1" "$mt" || { echo "merkle_tree_check failed"; exit 1; }
+# The batched secp256k1 multiplication's CPU twin (csrc/cpu/secp256k1.cpp) under ASan + UBSan against OpenSSL's
+# EC_POINT_mul: special scalars, 2,000 random rows, batches of 1 and 65536, the bad rows. A stand-alone program, at -O2:
+# the 65536-row batch is 300 million field multiplications.
+sp="$OUT/secp256k1_check"
+# shellcheck disable=SC2086
+"$CXX" "${FLAGS[@]}" -O2 ${SAN[asan]} "$ROOT/csrc/cpu/secp256k1.cpp" "$ROOT/tools/sanitize/secp256k1_check.cpp" -o "$sp" -lcrypto
+echo "== secp256k1: $sp"
+ASAN_OPTIONS="detect_leaks=1 abort_on_error=0" UBSAN_OPTIONS="print_stacktrace=1" "$sp" || { echo "secp256k1_check failed"; exit 1; }
 # libFuzzer (ASan + UBSan) over the SV2 frame scanner and the CPU hash paths.
 fz="$OUT/fuzz_native"
 "$CXX" -std=c++17 -O1 -g -march=x86-64-v2 "-I$ROOT/csrc/include" -fsanitize=fuzzer,address,undefined \
