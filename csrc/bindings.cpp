@@ -687,6 +687,65 @@ PYBIND11_MODULE(_native, m) {
     py_launch_secp256k1_mul(rows, n, out, stream);
   }, py::arg("rows"), py::arg("n"), py::arg("out"), py::arg("stream") = 0);
 
+  // Frame sealing: n heads and their data in one buffer -> the output regions (otedama/aead.h). The OpenSSL twin, the
+  // kernel's arithmetic compiled for the host (test entries, leading underscore), and the launches.
+  const auto seal_rows = [](const py::buffer& frames, uint32_t n,
+                            void (*fn)(const uint8_t*, size_t, uint32_t, uint8_t*, size_t)) {
+    // bytes, a bytearray or a memoryview: a caller that packs into a bytearray can wipe its keys afterwards
+    const py::buffer_info info = frames.request();
+    if (info.ndim != 1 || info.itemsize != 1 || (info.size && info.strides[0] != 1))
+      throw std::invalid_argument("frames: expected contiguous bytes");
+    std::string in(static_cast<const char*>(info.ptr), size_t(info.size));  // the caller's may change without the GIL
+    const auto* ip = reinterpret_cast<const uint8_t*>(in.data());
+    std::string out(aead_seal_check(ip, in.size(), n, 0), '\0');
+    {
+      py::gil_scoped_release r;  // a job's fan-out is two frames for every channel of the pool
+      fn(ip, in.size(), n, reinterpret_cast<uint8_t*>(&out[0]), out.size());
+    }
+    volatile char* wipe = &in[0];  // the copy held the keys
+    for (size_t i = 0; i < in.size(); ++i) wipe[i] = 0;
+    return py::bytes(out);
+  };
+  m.def("aead_seal_many_cpu", [seal_rows](const py::buffer& frames, uint32_t n) {
+    return seal_rows(frames, n, aead_seal_many_cpu);
+  }, py::arg("frames"), py::arg("n"));
+  m.def("_aead_seal_rows_host", [seal_rows](const py::buffer& frames, uint32_t n) {
+    return seal_rows(frames, n, aead_seal_rows_host);
+  }, py::arg("frames"), py::arg("n"));
+  m.def("_poly1305_rows_host", [](const py::buffer& rows) {
+    const py::buffer_info info = rows.request();
+    if (info.ndim != 1 || info.itemsize != 1 || (info.size && info.strides[0] != 1))
+      throw std::invalid_argument("rows: expected contiguous bytes");
+    const size_t size = size_t(info.size);
+    if (size == 0 || size % kPolyRowBytes) throw std::invalid_argument("rows: expected rows of 160 bytes");
+    std::string out(size / kPolyRowBytes * 16, '\0');
+    poly1305_rows_host(static_cast<const uint8_t*>(info.ptr), uint32_t(size / kPolyRowBytes),
+                       reinterpret_cast<uint8_t*>(&out[0]));
+    return py::bytes(out);
+  }, py::arg("rows"));
+  m.attr("SEAL_HEAD_BYTES") = kSealHeadBytes;
+  m.attr("SEAL_MAX_PLAIN") = kSealMaxPlain;
+  m.attr("SEAL_MAX_FRAMES") = kSealMaxFrames;
+  m.attr("POLY_ROW_BYTES") = kPolyRowBytes;
+  m.attr("POLY_MAX_MSG") = kPolyMaxMsg;
+  m.def("launch_aead_seal", [](uintptr_t frames, uint64_t in_bytes, uint32_t n, uintptr_t out, uint64_t out_bytes,
+                               uintptr_t stream) {
+    if (n == 0 || n > kSealMaxFrames) throw std::invalid_argument("need n in 1..2^24-1");
+    if (frames == 0 || out == 0) throw std::invalid_argument("need frames, out != 0");
+    if ((frames | out | in_bytes | out_bytes) & 15u)
+      throw std::invalid_argument("frames, out and their sizes must be multiples of 16");
+    if (in_bytes < uint64_t(n) * kSealHeadBytes || (in_bytes >> 32) || (out_bytes >> 32))
+      throw std::invalid_argument("frames holds n 64-byte heads; both buffers are below 4 GiB");
+    py_launch_aead_seal(frames, in_bytes, n, out, out_bytes, stream);
+  }, py::arg("frames"), py::arg("in_bytes"), py::arg("n"), py::arg("out"), py::arg("out_bytes"),
+     py::arg("stream") = 0);
+  m.def("_launch_poly1305_rows", [](uintptr_t rows, uint32_t n, uintptr_t tags, uintptr_t stream) {
+    if (n == 0 || n > kSealMaxFrames) throw std::invalid_argument("need n in 1..2^24-1");
+    if (rows == 0 || tags == 0) throw std::invalid_argument("need rows, tags != 0");
+    if ((rows | tags) & 15u) throw std::invalid_argument("rows and tags must be 16-byte aligned");
+    py_launch_poly1305_rows(rows, n, tags, stream);
+  }, py::arg("rows"), py::arg("n"), py::arg("tags"), py::arg("stream") = 0);
+
   py::class_<MinerBase, std::shared_ptr<MinerBase>>(m, "Miner")
       .def("start", &MinerBase::start, py::call_guard<py::gil_scoped_release>())
       .def("stop", &MinerBase::stop, py::call_guard<py::gil_scoped_release>())

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <string>
 
+#include "otedama/aead.h"
 #include "otedama/hitsink.h"
 #include "otedama/job.h"
 #include "otedama/merkle_tree.h"
@@ -82,6 +83,13 @@ void py_launch_merkle_tree(uintptr_t leaves, uint32_t t, uint32_t n, uintptr_t s
 // otedama/secp256k1.h): n 128-byte rows -> n 48-byte rows. Same conventions as above; both arrays are 16-byte aligned.
 void py_launch_secp256k1_mul(uintptr_t rows, uint32_t n, uintptr_t out, uintptr_t stream);
 
+// Frame sealing (otd_aead_seal of aead_seal.hip; heads, regions, limits and the CPU twin: otedama/aead.h): n heads and
+// their data in one input buffer -> each frame's tag and ciphertext in its region of the output. Same conventions as
+// above; both buffers are 16-byte aligned. otd_poly1305_rows is the test entry: n 160-byte rows -> n 16-byte tags.
+void py_launch_aead_seal(uintptr_t in, uint64_t in_bytes, uint32_t n, uintptr_t out, uint64_t out_bytes,
+                         uintptr_t stream);
+void py_launch_poly1305_rows(uintptr_t rows, uint32_t n, uintptr_t tags, uintptr_t stream);
+
 }  // namespace otedama
 
 #ifdef __HIPCC__
@@ -135,6 +143,12 @@ hipError_t launch_merkle_tree(const uint8_t* leaves, uint32_t t, uint32_t n, uin
 // secp256k1 multiplication: hipErrorInvalidValue, before launching anything, for n == 0 or above kSecpMaxRows, and a
 // null or not 16-byte aligned rows or out.
 hipError_t launch_secp256k1_mul(const uint8_t* rows, uint32_t n, uint8_t* out, hipStream_t s);
+// Frame sealing: hipErrorInvalidValue, before launching anything, for n == 0 or above kSealMaxFrames, a null or not
+// 16-byte aligned buffer, an input shorter than its n heads, and a buffer size that is no multiple of 16 or is 4 GiB
+// or more. The heads themselves are on the device: the kernel skips a lane whose head breaks the rules.
+hipError_t launch_aead_seal(const uint8_t* in, uint64_t in_bytes, uint32_t n, uint8_t* out, uint64_t out_bytes,
+                            hipStream_t s);
+hipError_t launch_poly1305_rows(const uint8_t* rows, uint32_t n, uint8_t* tags, hipStream_t s);
 
 }  // namespace otedama
 #endif

@@ -126,4 +126,17 @@ void py_launch_secp256k1_mul(uintptr_t rows, uint32_t n, uintptr_t out, uintptr_
             "launch_secp256k1_mul");
 }
 
+void py_launch_aead_seal(uintptr_t in, uint64_t in_bytes, uint32_t n, uintptr_t out, uint64_t out_bytes,
+                         uintptr_t stream) {
+  hip_check(launch_aead_seal(reinterpret_cast<const uint8_t*>(in), in_bytes, n, reinterpret_cast<uint8_t*>(out),
+                             out_bytes, reinterpret_cast<hipStream_t>(stream)),
+            "launch_aead_seal");
+}
+
+void py_launch_poly1305_rows(uintptr_t rows, uint32_t n, uintptr_t tags, uintptr_t stream) {
+  hip_check(launch_poly1305_rows(reinterpret_cast<const uint8_t*>(rows), n, reinterpret_cast<uint8_t*>(tags),
+                                 reinterpret_cast<hipStream_t>(stream)),
+            "launch_poly1305_rows");
+}
+
 }  // namespace otedama

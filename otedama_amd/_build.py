@@ -34,6 +34,7 @@ HIP_SOURCES = [
     "kernels/channel_roots.hip",
     "kernels/merkle_tree.hip",
     "kernels/secp256k1_mul.hip",
+    "kernels/aead_seal.hip",
     "runtime/gpu_miner.hip",
     "runtime/ops_launch.hip",
 ]

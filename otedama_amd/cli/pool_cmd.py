@@ -42,7 +42,8 @@ def apply_config_file(fs: FlagSet, stderr: TextIO) -> None:
              ("template-file", ps.template_file), ("template-device", ps.template_device),
              ("template-min-gpu", ps.template_min_gpu), ("handshake-device", ps.handshake_device),
              ("handshake-batch-ms", ps.handshake_batch_ms), ("handshake-batch-max", ps.handshake_batch_max),
-             ("handshake-min-gpu", ps.handshake_min_gpu), ("http-addr", cfg.http_addr))
+             ("handshake-min-gpu", ps.handshake_min_gpu), ("seal-device", ps.seal_device),
+             ("seal-min-gpu", ps.seal_min_gpu), ("http-addr", cfg.http_addr))
     default = type(ps)()
     for flag, value in pairs:
         unset_in_file = flag != "http-addr" and value == getattr(default, _FILE_FIELD[flag])
@@ -61,7 +62,8 @@ _FILE_FIELD = {"algorithms": "algorithm", "listen-sv2": "listen_sv2", "listen-v1
                "template-file": "template_file", "template-device": "template_device",
                "template-min-gpu": "template_min_gpu", "handshake-device": "handshake_device",
                "handshake-batch-ms": "handshake_batch_ms", "handshake-batch-max": "handshake_batch_max",
-               "handshake-min-gpu": "handshake_min_gpu"}
+               "handshake-min-gpu": "handshake_min_gpu", "seal-device": "seal_device",
+               "seal-min-gpu": "seal_min_gpu"}
 
 
 def verify_options(fs: FlagSet) -> dict:
@@ -130,6 +132,21 @@ def handshake_options_error(opts: dict) -> str | None:
     return None
 
 
+def seal_options(fs: FlagSet) -> dict:
+    """The frame sealer's PoolOptions fields from the (file-filled) flags."""
+    return {"seal_device": fs["seal-device"], "seal_min_gpu": fs["seal-min-gpu"]}
+
+
+def seal_options_error(opts: dict) -> str | None:
+    from otedama_amd.pool.devicepath import valid_device
+
+    if not valid_device(opts["seal_device"]):
+        return f"--seal-device {opts['seal_device']!r} must be empty (off), cpu or cuda:N"
+    if opts["seal_min_gpu"] < 0:
+        return "--seal-min-gpu must not be negative (0 = the measured default)"
+    return None
+
+
 def template_source(fs: FlagSet):
     """The pool's template source from the flags: a ``GbtFileSource`` over ``--template-file`` paying
     ``--payout-address`` (OP_RETURN without one), or None for the synthetic chain."""
@@ -176,6 +193,8 @@ def pool_flags(stderr: TextIO) -> FlagSet:
     fs.float("handshake-batch-ms", 2.0, "Handshake batch flush delay after the oldest waiting handshake, in milliseconds.")
     fs.int("handshake-batch-max", 4096, "Handshake batch flush size.")
     fs.int("handshake-min-gpu", 0, "Batches of fewer handshakes are computed on the CPU (0 = the measured default).")
+    fs.string("seal-device", "", "With --sv2-noise, a job's frames sealed in one batch: cpu or cuda:N (empty = off, sealed one by one).")
+    fs.int("seal-min-gpu", 0, "Jobs of fewer frames are sealed on the CPU (0 = the measured default).")
     fs.string("config", "", "Path to the YAML config file (default: $OTEDAMA_CONFIG or ~/.config/otedama/config.yaml).")
     return fs
 
@@ -199,7 +218,8 @@ def cmd_pool(args: list[str], stdout: TextIO, stderr: TextIO) -> int:
             stderr.write(f"pool: payout address invalid: {err}\n")
             return EXIT_CONFIG
     err = verify_options_error(verify_options(fs)) or job_options_error(job_options(fs)) \
-        or template_options_error(template_options(fs)) or handshake_options_error(handshake_options(fs))
+        or template_options_error(template_options(fs)) or handshake_options_error(handshake_options(fs)) \
+        or seal_options_error(seal_options(fs))
     if err:
         stderr.write(f"pool: {err}\n")
         return EXIT_CONFIG
@@ -243,7 +263,7 @@ async def _serve(fs, algos: list[str], stdout: TextIO) -> int:
                            dialect=fs["dialect"], noise=fs["sv2-noise"], noise_suite=fs["noise-suite"],
                            coinbase_message=fs.values.get("coinbase-message", PoolOptions.coinbase_message),
                            noise_authority_secret=int(fs["noise-authority-key"] or "0", 16), **verify_options(fs), **job_options(fs),
-                           **template_options(fs), **handshake_options(fs))
+                           **template_options(fs), **handshake_options(fs), **seal_options(fs))
 
         def log(level, msg):
             stdout.write(f"[{level}] {msg}\n")

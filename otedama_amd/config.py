@@ -111,6 +111,9 @@ class PoolServerConfig:
     handshake_batch_ms: float = 2.0     # flush this long after the oldest waiting handshake
     handshake_batch_max: int = 4096     # flush at this many waiting handshakes
     handshake_min_gpu: int = 0          # fewer handshakes than this are computed on the CPU; 0 = the measured default
+    # a job's Noise frames sealed in one batch (pool/frameseal.py); "" = off
+    seal_device: str = ""               # "", "cpu" or "cuda:N"
+    seal_min_gpu: int = 0               # jobs of fewer frames are sealed on the CPU; 0 = the measured default
 
 
 @dataclass
@@ -220,6 +223,10 @@ class Config:
             issues.append("pool_server.handshake_batch_max must be in 1..21845 (three rows a handshake, 65536 a call)")
         if ps.handshake_min_gpu < 0:
             issues.append("pool_server.handshake_min_gpu must be >= 0 (0 = the measured default)")
+        if not valid_device(str(ps.seal_device)):
+            issues.append(f"pool_server.seal_device {ps.seal_device!r} is not one of \"\", cpu, cuda:N")
+        if ps.seal_min_gpu < 0:
+            issues.append("pool_server.seal_min_gpu must be >= 0 (0 = the measured default)")
         if issues:
             raise ConfigError("config validation failed:\n  - " + "\n  - ".join(issues))
 

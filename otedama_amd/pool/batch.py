@@ -7,7 +7,8 @@ compares happen on the GPU. Both paths return the same list. Importing this modu
 native extension.
 
 :func:`channel_roots` is the same three-way choice for a job's fan-out to Stratum V2 standard channels: one job and
-n extranonce prefixes in, n merkle roots out.
+n extranonce prefixes in, n merkle roots out. :func:`seal_frames` is the same choice for that fan-out's Noise frames:
+n plaintexts with n keys and counters in, n sealed frames out.
 """
 from __future__ import annotations
 
@@ -127,6 +128,55 @@ def channel_roots(job: ShareJob, prefixes: Sequence[bytes], device=None) -> list
             if prepared is not None:  # as above
                 return op.roots(prepared, prefixes)
     return [root_of(job, p) for p in prefixes]
+
+
+def seal_frames(frames: Sequence[tuple], device=None) -> list[bytes]:
+    """The Noise transport's seal of every ``(key32, counter, plaintext)`` frame, in order: the bytes
+    ``noise.CipherState.encrypt`` returns for that key and counter (ChaCha20-Poly1305, empty associated data, nonce
+    four zero bytes and the counter little-endian). ``device=None``: ``utils.aead.seal``, one frame at a time.
+    ``"cpu"``: the native ``aead_seal_many_cpu``, one call. ``"cuda:N"``: one ``ops.seal.FrameSeal.seal`` round trip
+    on that GPU. A frame over ``SEAL_MAX_PLAIN`` bytes is sealed by ``utils.aead.seal`` whatever the device, in its
+    place in the order."""
+    from otedama_amd.ops.seal_rows import SEAL_MAX_PLAIN, pack_frames, unpack_sealed, wipe_keys
+    from otedama_amd.utils import aead
+
+    def one(key, counter, plain):
+        if not 0 <= counter < (1 << 64) - 1:
+            raise ValueError("a counter is in [0, 2^64 - 1)")
+        return aead.seal(aead.CHACHA20POLY1305, key, b"\x00" * 4 + struct.pack("<Q", counter), plain)
+
+    frames = list(frames)
+    if device is None or not frames:
+        return [one(*f) for f in frames]
+    small = [i for i, f in enumerate(frames) if len(f[2]) <= SEAL_MAX_PLAIN]
+    whole = len(small) == len(frames)  # the usual case: no copy of the list, no merge afterwards
+    out: list = [None] * len(frames)
+    if small:
+        batch = frames if whole else [frames[i] for i in small]
+        if str(device) == "cpu":
+            from otedama_amd.ops.native import require_native
+
+            packed, _out_bytes = pack_frames(batch)
+            try:
+                sealed = unpack_sealed(packed, require_native().aead_seal_many_cpu(packed, len(batch)), len(batch))
+            finally:
+                wipe_keys(packed, len(batch))
+        else:
+            from otedama_amd.ops.seal import FrameSeal  # imports torch
+
+            key = ("seal", "", str(device))
+            op = _ops.get(key)
+            if op is None:
+                op = _ops[key] = FrameSeal(device)
+            sealed = op.seal(batch)
+        if whole:
+            return sealed
+        for i, s in zip(small, sealed):
+            out[i] = s
+    for i, f in enumerate(frames):
+        if out[i] is None:
+            out[i] = one(*f)
+    return out
 
 
 def template_tree(txids: Sequence[bytes], wtxids: Sequence[bytes] = (), device=None):

@@ -100,6 +100,11 @@ class PoolOptions:
     handshake_batch_ms: float = 2.0   # flush this long after the oldest waiting handshake
     handshake_batch_max: int = 4096   # flush at this many waiting handshakes (three rows each)
     handshake_min_gpu: int = 0        # a flush of fewer handshakes is computed on the CPU; 0 = the default
+    # A job's Noise frames in one batch (pool/frameseal.py), with `noise` on. "" = off: every message of the SV2
+    # fan-out is sealed on its own on the event loop, as before. "cpu": all frames of a job in one native call.
+    # "cuda:N": in one launch on that GPU (ops.seal.FrameSeal.seal).
+    seal_device: str = ""
+    seal_min_gpu: int = 0             # a job of fewer frames is sealed on the CPU; 0 = the default
 
 
 @dataclass
@@ -236,6 +241,10 @@ class PoolServer:
         # `handshake_mul_fn` replaces its device path (tests inject one; None = Secp256k1Mul.mul on that device)
         self._handshakes = None
         self.handshake_mul_fn = None
+        # the frame sealer, made by the first _make_job when opts.seal_device is set and Noise is on; `seal_fn`
+        # replaces its configured path (tests inject one; None = FrameSeal.seal on opts.seal_device)
+        self._sealer = None
+        self.seal_fn = None
         self._branches_of: BlockTemplate | None = None  # the block whose merkle branches are cached below
         self._branches: list[bytes] = []
         self._init_metrics(registry)
@@ -301,6 +310,8 @@ class PoolServer:
             self._job_roots.close()
         if self._template_tree is not None:
             self._template_tree.close()
+        if self._sealer is not None:
+            self._sealer.close()
         self._hash_pool.shutdown(wait=False, cancel_futures=True)
         self.journal.close()
 
@@ -378,6 +389,15 @@ class PoolServer:
             c.send_job(job)
         v2 = list(self._v2)
         roots = self._standard_roots(job, v2) if self.opts.job_device else {}
+        if self.opts.seal_device and self.opts.noise and v2:  # the frames of all of them sealed in one call
+            if self._sealer is None:
+                from otedama_amd.pool.frameseal import FrameSealer
+
+                self._sealer = FrameSealer(self, device_seal=self.seal_fn)
+            with self._sealer.corked(v2):
+                for c in v2:
+                    c.send_job(job, roots.get(c))
+            return job
         for c in v2:
             c.send_job(job, roots.get(c))
         return job
@@ -741,6 +761,14 @@ class PoolServer:
         return {"device": self.opts.handshake_device, "enabled": False, "batches": 0, "gpu_handshakes": 0,
                 "cpu_handshakes": 0, "last_batch": 0, "max_batch": 0, "last_ms": 0.0, "device_errors": 0}
 
+    def seal_stats(self) -> dict:
+        """The ``seal`` object of /api/v1/pool: the frame sealer's device, whether the configured path is in use
+        (False when the feature is off, and after a device error has turned a GPU path off), and its counters."""
+        if self._sealer is not None:
+            return self._sealer.stats()
+        return {"device": self.opts.seal_device, "enabled": False, "batches": 0, "gpu_frames": 0, "cpu_frames": 0,
+                "last_frames": 0, "last_ms": 0.0, "device_errors": 0}
+
     def _get_handshakes(self):
         if self._handshakes is None:
             from otedama_amd.pool.handshakes import HandshakeBatcher
@@ -765,6 +793,7 @@ class PoolServer:
             "jobs": self.jobs_stats(),
             "template": self.template_stats(),
             "handshake": self.handshake_stats(),
+            "seal": self.seal_stats(),
             "new_block_at": list(self.new_block_at)[-64:],
             # per live connection: the difficulty in force, how often vardiff moved it, and when it last moved
             # (seconds after the channel opened: the time vardiff took to reach the difficulty it holds)

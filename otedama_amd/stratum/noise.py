@@ -93,6 +93,16 @@ class CipherState:
             raise NoiseError("noise: nonce exhausted")
         return b"\x00" * 4 + struct.pack("<Q", self.n)
 
+    def reserve(self) -> int:
+        """The counter the next encryption must use, which is then consumed: for a caller that seals the frame
+        elsewhere (``EncryptedWriter.cork``). A reserved counter whose frame never reaches the peer desynchronises
+        the connection."""
+        if self.n >= 2 ** 64 - 1:
+            raise NoiseError("noise: nonce exhausted")
+        n = self.n
+        self.n += 1
+        return n
+
     def encrypt(self, ad: bytes, plain: bytes) -> bytes:
         if self.k is None:
             return plain
@@ -383,11 +393,42 @@ class EncryptedWriter:
 
     def __init__(self, writer: asyncio.StreamWriter, cs: CipherState):
         self._w, self._cs = writer, cs
+        self._batch: list | None = None  # corked: write() queues its frames here, unsealed
+
+    def cork(self, batch: list) -> bool:
+        """Until :meth:`uncork`, :meth:`write` does everything but encrypt: per frame it checks the size, reserves
+        the counter and appends ``(writer, key, counter, plaintext)`` to ``batch``. Whoever corked seals the batch
+        (``pool.batch.seal_frames``) and writes ``u16 length || sealed`` of every entry to ``writer.transport`` in
+        queue order before uncorking, so the peer sees the counters in order. An unkeyed writer never corks: False."""
+        if self._cs.k is None:
+            return False
+        self._batch = batch
+        return True
+
+    def uncork(self) -> None:
+        self._batch = None
+
+    @property
+    def transport(self):
+        """The writer underneath, which takes the sealed frames of a corked batch."""
+        return self._w
 
     def write(self, data: bytes) -> None:
         step = MAX_FRAME - TAG
         for off in range(0, max(len(data), 1), step):
-            self._w.write(encode_frame(self._cs, data[off:off + step]))
+            chunk = data[off:off + step]
+            if self._batch is None:
+                self._w.write(encode_frame(self._cs, chunk))
+            else:
+                self._queue(chunk)
+
+    def _queue(self, chunk: bytes) -> None:
+        """One frame of a corked write. As encode_frame: the size check first, so that a refused frame consumes no
+        counter."""
+        if len(chunk) + TAG > MAX_FRAME:
+            raise NoiseError(f"noise: message too large: {len(chunk) + TAG}-byte ciphertext exceeds {MAX_FRAME} "
+                             f"(plaintext {len(chunk)})")
+        self._batch.append((self, self._cs.k, self._cs.reserve(), bytes(chunk)))
 
     async def drain(self) -> None:
         await self._w.drain()

@@ -53,6 +53,14 @@ sp="$OUT/secp256k1_check"
 "$CXX" "${FLAGS[@]}" -O2 ${SAN[asan]} "$ROOT/csrc/cpu/secp256k1.cpp" "$ROOT/tools/sanitize/secp256k1_check.cpp" -o "$sp" -lcrypto
 echo "== secp256k1: $sp"
 ASAN_OPTIONS="detect_leaks=1 abort_on_error=0" UBSAN_OPTIONS="print_stacktrace=1" "$sp" || { echo "secp256k1_check failed"; exit 1; }
+# The frame seal's arithmetic (csrc/include/otedama/chacha_poly.h, what the gfx950 kernel runs) and its OpenSSL twin
+# (csrc/cpu/aead.cpp) under ASan + UBSan against one EVP seal a frame: every length 0..130 and the block edges, batches
+# of 1 to 257, Poly1305 rows against the big-integer table and OpenSSL, the refused heads. A stand-alone program.
+cp="$OUT/chacha_poly_check"
+# shellcheck disable=SC2086
+"$CXX" "${FLAGS[@]}" ${SAN[asan]} "$ROOT/csrc/cpu/aead.cpp" "$ROOT/tools/sanitize/chacha_poly_check.cpp" -o "$cp" -lcrypto
+echo "== chacha20-poly1305: $cp"
+ASAN_OPTIONS="detect_leaks=1 abort_on_error=0" UBSAN_OPTIONS="print_stacktrace=1" "$cp" || { echo "chacha_poly_check failed"; exit 1; }
 # libFuzzer (ASan + UBSan) over the SV2 frame scanner and the CPU hash paths.
 fz="$OUT/fuzz_native"
 "$CXX" -std=c++17 -O1 -g -march=x86-64-v2 "-I$ROOT/csrc/include" -fsanitize=fuzzer,address,undefined \
