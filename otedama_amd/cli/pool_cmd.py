@@ -12,12 +12,14 @@ defaults: an explicitly given flag always wins.
 from __future__ import annotations
 
 import asyncio
+import functools
 import json
 import signal
 from typing import TextIO
 
 from otedama_amd.cli.flags import FlagSet
 from otedama_amd.cli.main import EXIT_CONFIG, EXIT_OK, EXIT_RUNTIME, parse_subcommand
+from otedama_amd.pool.devicepath import PATHS, valid_device
 
 
 def _bump(addr: str, k: int) -> str:
@@ -33,118 +35,51 @@ def apply_config_file(fs: FlagSet, stderr: TextIO) -> None:
 
     cfg = load_config(fs, stderr)
     ps = cfg.pool_server
-    pairs = (("algorithms", ps.algorithm), ("listen-sv2", ps.listen_sv2), ("listen-v1", ps.listen_v1),
-             ("difficulty", ps.initial_difficulty), ("share-seconds", ps.target_share_seconds),
-             ("retarget-seconds", ps.vardiff_retarget_seconds), ("journal", ps.journal_path),
-             ("verify-device", ps.verify_device), ("verify-batch-ms", ps.verify_batch_ms),
-             ("verify-batch-max", ps.verify_batch_max), ("verify-min-gpu", ps.verify_min_gpu),
-             ("job-device", ps.job_device), ("job-min-gpu", ps.job_min_gpu),
-             ("template-file", ps.template_file), ("template-device", ps.template_device),
-             ("template-min-gpu", ps.template_min_gpu), ("handshake-device", ps.handshake_device),
-             ("handshake-batch-ms", ps.handshake_batch_ms), ("handshake-batch-max", ps.handshake_batch_max),
-             ("handshake-min-gpu", ps.handshake_min_gpu), ("seal-device", ps.seal_device),
-             ("seal-min-gpu", ps.seal_min_gpu), ("http-addr", cfg.http_addr))
     default = type(ps)()
-    for flag, value in pairs:
-        unset_in_file = flag != "http-addr" and value == getattr(default, _FILE_FIELD[flag])
-        if flag in fs.set_flags or unset_in_file or value in ("", None):
+    pairs = [(flag, getattr(ps, field), getattr(default, field)) for flag, field in _FILE_FIELD.items()]
+    for flag, value, unset in pairs + [("http-addr", cfg.http_addr, "")]:
+        if flag in fs.set_flags or value == unset or value in ("", None):
             continue
         fs.values[flag] = value
     fs.values["coinbase-message"] = ps.coinbase_message
 
 
+def _flag(field: str) -> str:
+    return field.replace("_", "-")
+
+
+# flag -> the pool_server field of the config file that fills it
 _FILE_FIELD = {"algorithms": "algorithm", "listen-sv2": "listen_sv2", "listen-v1": "listen_v1",
                "difficulty": "initial_difficulty", "share-seconds": "target_share_seconds",
                "retarget-seconds": "vardiff_retarget_seconds", "journal": "journal_path",
-               "verify-device": "verify_device", "verify-batch-ms": "verify_batch_ms",
-               "verify-batch-max": "verify_batch_max", "verify-min-gpu": "verify_min_gpu",
-               "job-device": "job_device", "job-min-gpu": "job_min_gpu",
-               "template-file": "template_file", "template-device": "template_device",
-               "template-min-gpu": "template_min_gpu", "handshake-device": "handshake_device",
-               "handshake-batch-ms": "handshake_batch_ms", "handshake-batch-max": "handshake_batch_max",
-               "handshake-min-gpu": "handshake_min_gpu", "seal-device": "seal_device",
-               "seal-min-gpu": "seal_min_gpu"}
+               "template-file": "template_file",
+               **{_flag(field): field for spec in PATHS.values() for field in spec.fields}}
 
 
-def verify_options(fs: FlagSet) -> dict:
-    """The micro-batcher's PoolOptions fields from the (file-filled) flags."""
-    return {"verify_device": fs["verify-device"], "verify_batch_ms": fs["verify-batch-ms"],
-            "verify_batch_max": fs["verify-batch-max"], "verify_min_gpu": fs["verify-min-gpu"]}
+def _options(spec, fs: FlagSet) -> dict:
+    """The PoolOptions fields of one CPU-or-GPU path (pool/devicepath.py PATHS) from the (file-filled) flags."""
+    return {field: fs[_flag(field)] for field in spec.fields}
 
 
-def verify_options_error(opts: dict) -> str | None:
-    from otedama_amd.pool.devicepath import valid_device
-
-    if not valid_device(opts["verify_device"]):
-        return f"--verify-device {opts['verify_device']!r} must be empty (off), cpu or cuda:N"
-    if opts["verify_batch_ms"] <= 0 or opts["verify_batch_max"] <= 0:
-        return "--verify-batch-ms and --verify-batch-max must be positive"
-    if opts["verify_min_gpu"] < 0:
-        return "--verify-min-gpu must not be negative (0 = the algorithm's measured default)"
+def _options_error(spec, opts: dict) -> str | None:
+    device, min_gpu = f"{spec.prefix}_device", f"{spec.prefix}_min_gpu"
+    if not valid_device(opts[device]):
+        return f"--{_flag(device)} {opts[device]!r} must be empty (off), cpu or cuda:N"
+    if spec.batched:
+        ms, most = f"{spec.prefix}_batch_ms", f"{spec.prefix}_batch_max"
+        if opts[ms] <= 0 or not spec.batch_max_ok(opts[most]):
+            return (f"--{_flag(ms)} must be positive and --{_flag(most)} in 1..{spec.batch_max_limit}"
+                    if spec.batch_max_limit else f"--{_flag(ms)} and --{_flag(most)} must be positive")
+    if opts[min_gpu] < 0:
+        default = "the algorithm's measured default" if spec.per_algorithm else "the measured default"
+        return f"--{_flag(min_gpu)} must not be negative (0 = {default})"
     return None
 
 
-def job_options(fs: FlagSet) -> dict:
-    """The job fan-out's PoolOptions fields from the (file-filled) flags."""
-    return {"job_device": fs["job-device"], "job_min_gpu": fs["job-min-gpu"]}
-
-
-def job_options_error(opts: dict) -> str | None:
-    from otedama_amd.pool.devicepath import valid_device
-
-    if not valid_device(opts["job_device"]):
-        return f"--job-device {opts['job_device']!r} must be empty (off), cpu or cuda:N"
-    if opts["job_min_gpu"] < 0:
-        return "--job-min-gpu must not be negative (0 = the measured default)"
-    return None
-
-
-def template_options(fs: FlagSet) -> dict:
-    """The template tree's PoolOptions fields from the (file-filled) flags."""
-    return {"template_device": fs["template-device"], "template_min_gpu": fs["template-min-gpu"]}
-
-
-def template_options_error(opts: dict) -> str | None:
-    from otedama_amd.pool.devicepath import valid_device
-
-    if not valid_device(opts["template_device"]):
-        return f"--template-device {opts['template_device']!r} must be empty (off), cpu or cuda:N"
-    if opts["template_min_gpu"] < 0:
-        return "--template-min-gpu must not be negative (0 = the measured default)"
-    return None
-
-
-def handshake_options(fs: FlagSet) -> dict:
-    """The handshake batcher's PoolOptions fields from the (file-filled) flags."""
-    return {"handshake_device": fs["handshake-device"], "handshake_batch_ms": fs["handshake-batch-ms"],
-            "handshake_batch_max": fs["handshake-batch-max"], "handshake_min_gpu": fs["handshake-min-gpu"]}
-
-
-def handshake_options_error(opts: dict) -> str | None:
-    from otedama_amd.pool.devicepath import valid_device
-
-    if not valid_device(opts["handshake_device"]):
-        return f"--handshake-device {opts['handshake_device']!r} must be empty (off), cpu or cuda:N"
-    if opts["handshake_batch_ms"] <= 0 or not 0 < opts["handshake_batch_max"] <= 21845:
-        return "--handshake-batch-ms must be positive and --handshake-batch-max in 1..21845"
-    if opts["handshake_min_gpu"] < 0:
-        return "--handshake-min-gpu must not be negative (0 = the measured default)"
-    return None
-
-
-def seal_options(fs: FlagSet) -> dict:
-    """The frame sealer's PoolOptions fields from the (file-filled) flags."""
-    return {"seal_device": fs["seal-device"], "seal_min_gpu": fs["seal-min-gpu"]}
-
-
-def seal_options_error(opts: dict) -> str | None:
-    from otedama_amd.pool.devicepath import valid_device
-
-    if not valid_device(opts["seal_device"]):
-        return f"--seal-device {opts['seal_device']!r} must be empty (off), cpu or cuda:N"
-    if opts["seal_min_gpu"] < 0:
-        return "--seal-min-gpu must not be negative (0 = the measured default)"
-    return None
+# verify_options(fs), verify_options_error(opts), and the same for job, template, handshake and seal
+for _spec in PATHS.values():
+    globals()[f"{_spec.prefix}_options"] = functools.partial(_options, _spec)
+    globals()[f"{_spec.prefix}_options_error"] = functools.partial(_options_error, _spec)
 
 
 def template_source(fs: FlagSet):
@@ -217,9 +152,7 @@ def cmd_pool(args: list[str], stdout: TextIO, stderr: TextIO) -> int:
         if err:
             stderr.write(f"pool: payout address invalid: {err}\n")
             return EXIT_CONFIG
-    err = verify_options_error(verify_options(fs)) or job_options_error(job_options(fs)) \
-        or template_options_error(template_options(fs)) or handshake_options_error(handshake_options(fs)) \
-        or seal_options_error(seal_options(fs))
+    err = next(filter(None, (_options_error(spec, _options(spec, fs)) for spec in PATHS.values())), None)
     if err:
         stderr.write(f"pool: {err}\n")
         return EXIT_CONFIG
@@ -262,8 +195,8 @@ async def _serve(fs, algos: list[str], stdout: TextIO) -> int:
                            journal_path=journal or ":memory:", payout_scheme=fs["payout-scheme"],
                            dialect=fs["dialect"], noise=fs["sv2-noise"], noise_suite=fs["noise-suite"],
                            coinbase_message=fs.values.get("coinbase-message", PoolOptions.coinbase_message),
-                           noise_authority_secret=int(fs["noise-authority-key"] or "0", 16), **verify_options(fs), **job_options(fs),
-                           **template_options(fs), **handshake_options(fs), **seal_options(fs))
+                           noise_authority_secret=int(fs["noise-authority-key"] or "0", 16),
+                           **{k: v for spec in PATHS.values() for k, v in _options(spec, fs).items()})
 
         def log(level, msg):
             stdout.write(f"[{level}] {msg}\n")

@@ -197,36 +197,21 @@ class Config:
         if self.pool_server.target_share_seconds <= 0:
             issues.append("pool_server.target_share_seconds must be > 0")
         ps = self.pool_server
-        from otedama_amd.pool.devicepath import valid_device  # torch-free; the one statement of the device grammar
+        from otedama_amd.pool.devicepath import PATHS, valid_device  # torch-free; the one statement of these options
 
-        if not valid_device(str(ps.verify_device)):
-            issues.append(f"pool_server.verify_device {ps.verify_device!r} is not one of \"\", cpu, cuda:N")
-        if ps.verify_batch_ms <= 0:
-            issues.append("pool_server.verify_batch_ms must be > 0")
-        if ps.verify_batch_max <= 0:
-            issues.append("pool_server.verify_batch_max must be > 0")
-        if ps.verify_min_gpu < 0:
-            issues.append("pool_server.verify_min_gpu must be >= 0 (0 = the algorithm's default)")
-        if not valid_device(str(ps.job_device)):
-            issues.append(f"pool_server.job_device {ps.job_device!r} is not one of \"\", cpu, cuda:N")
-        if ps.job_min_gpu < 0:
-            issues.append("pool_server.job_min_gpu must be >= 0 (0 = the measured default)")
-        if not valid_device(str(ps.template_device)):
-            issues.append(f"pool_server.template_device {ps.template_device!r} is not one of \"\", cpu, cuda:N")
-        if ps.template_min_gpu < 0:
-            issues.append("pool_server.template_min_gpu must be >= 0 (0 = the measured default)")
-        if not valid_device(str(ps.handshake_device)):
-            issues.append(f"pool_server.handshake_device {ps.handshake_device!r} is not one of \"\", cpu, cuda:N")
-        if ps.handshake_batch_ms <= 0:
-            issues.append("pool_server.handshake_batch_ms must be > 0")
-        if not 0 < ps.handshake_batch_max <= 21845:
-            issues.append("pool_server.handshake_batch_max must be in 1..21845 (three rows a handshake, 65536 a call)")
-        if ps.handshake_min_gpu < 0:
-            issues.append("pool_server.handshake_min_gpu must be >= 0 (0 = the measured default)")
-        if not valid_device(str(ps.seal_device)):
-            issues.append(f"pool_server.seal_device {ps.seal_device!r} is not one of \"\", cpu, cuda:N")
-        if ps.seal_min_gpu < 0:
-            issues.append("pool_server.seal_min_gpu must be >= 0 (0 = the measured default)")
+        for spec in PATHS.values():  # the pool's CPU-or-GPU paths, one set of rules for all
+            value = spec.values(ps)
+            name = f"pool_server.{spec.prefix}"
+            if not valid_device(str(value["device"])):
+                issues.append(f"{name}_device {value['device']!r} is not one of \"\", cpu, cuda:N")
+            if spec.batched and value["batch_ms"] <= 0:
+                issues.append(f"{name}_batch_ms must be > 0")
+            if spec.batched and not spec.batch_max_ok(value["batch_max"]):
+                issues.append(f"{name}_batch_max must be in 1..{spec.batch_max_limit}{spec.batch_max_why}"
+                              if spec.batch_max_limit else f"{name}_batch_max must be > 0")
+            if value["min_gpu"] < 0:
+                default = "the algorithm's default" if spec.per_algorithm else "the measured default"
+                issues.append(f"{name}_min_gpu must be >= 0 (0 = {default})")
         if issues:
             raise ConfigError("config validation failed:\n  - " + "\n  - ".join(issues))
 

@@ -33,7 +33,7 @@ class ShareJob:
     branches: list = field(default_factory=list)
 
 
-_ops: dict[tuple, object] = {}  # (kind, algorithm, device) -> ops.verify.ShareVerify or ops.roots.ChannelRoots
+_ops: dict[tuple, object] = {}  # (kind, algorithm, device) -> the process's op of that kind on that device
 
 
 def prepared_or_none(prepare, job: ShareJob):
@@ -45,11 +45,17 @@ def prepared_or_none(prepare, job: ShareJob):
         return None
 
 
-def _op_and_block(key: tuple, make_op, job: ShareJob):
-    """The process's op for ``key`` (made on first use) and ``job``'s block prepared on its device, or ``None``."""
+def _op(key: tuple, make_op):
+    """The process's op for ``key``, made on first use."""
     op = _ops.get(key)
     if op is None:
         op = _ops[key] = make_op()
+    return op
+
+
+def _op_and_block(key: tuple, make_op, job: ShareJob):
+    """The process's op for ``key`` and ``job``'s block prepared on its device, or ``None``."""
+    op = _op(key, make_op)
     return op, prepared_or_none(op.prepare, job)
 
 
@@ -164,11 +170,7 @@ def seal_frames(frames: Sequence[tuple], device=None) -> list[bytes]:
         else:
             from otedama_amd.ops.seal import FrameSeal  # imports torch
 
-            key = ("seal", "", str(device))
-            op = _ops.get(key)
-            if op is None:
-                op = _ops[key] = FrameSeal(device)
-            sealed = op.seal(batch)
+            sealed = _op(("seal", "", str(device)), lambda: FrameSeal(device)).seal(batch)
         if whole:
             return sealed
         for i, s in zip(small, sealed):
@@ -205,10 +207,6 @@ def template_tree(txids: Sequence[bytes], wtxids: Sequence[bytes] = (), device=N
         else:
             from otedama_amd.ops.merkle import MerkleTree  # imports torch
 
-            key = ("tree", "", str(device))
-            op = _ops.get(key)
-            if op is None:
-                op = _ops[key] = MerkleTree(device)
-            out = op.tree(trees)
+            out = _op(("tree", "", str(device)), lambda: MerkleTree(device)).tree(trees)
         return out[0][1], (out[1][0] if wtxids else None)
     return merkle_branches(txids), (merkle_root_full([bytes(32)] + wtxids) if wtxids else None)

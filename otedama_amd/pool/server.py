@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import asyncio
 import concurrent.futures
+import importlib
 import json
 import os
 import struct
@@ -33,6 +34,7 @@ from dataclasses import dataclass, field
 from otedama_amd.metrics import Registry
 from otedama_amd.models import algorithms
 from otedama_amd.models.header import TargetError, hash_to_int, target_from_difficulty, target_from_nbits
+from otedama_amd.pool.devicepath import PATHS
 from otedama_amd.pool.journal import Journal, ShareRow
 from otedama_amd.pool.template import BlockTemplate, TemplateSource, merkle_root_from_branches
 from otedama_amd.pool.vardiff import Vardiff, VardiffConfig, VardiffState
@@ -47,6 +49,13 @@ MAX_NTIME_FUTURE = 7200
 RETARGET_GRACE = 10.0
 SETTLE_BAND = 0.25  # a retarget that moves the difficulty by more than this fraction means the worker is converging
 MAX_SHARES_PER_JOB = 1 << 20  # credited headers kept per live job before the job is retired
+# Where PoolServer keeps each path of pool/devicepath.py PATHS, by option prefix: its attribute, the attribute that
+# injects a device call, and the pool/ module and class that is made on first use.
+_PATH_HOME = {"verify": ("_batcher", "verify_hasher", "microbatch", "ShareBatcher"),
+              "job": ("_job_roots", "job_roots_fn", "jobroots", "JobRoots"),
+              "template": ("_template_tree", "template_tree_fn", "templatetree", "TemplateTree"),
+              "handshake": ("_handshakes", "handshake_mul_fn", "handshakes", "HandshakeBatcher"),
+              "seal": ("_sealer", "seal_fn", "frameseal", "FrameSealer")}
 
 
 @dataclass
@@ -225,26 +234,12 @@ class PoolServer:
         # CLOCK_MONOTONIC time each new block's clean job was handed to every connection (a node's job-switch probe
         # times each rank's device from here: parallel/node_probe.py)
         self.new_block_at: deque = deque(maxlen=256)
-        # the micro-batcher, made by the first validate_async when opts.verify_device is set; `verify_hasher`
-        # replaces its device path (tests inject one; None = ShareVerify.results on opts.verify_device)
-        self._batcher = None
-        self.verify_hasher = None
-        # the job fan-out, made by the first _make_job when opts.job_device is set; `job_roots_fn` replaces its
-        # device path (tests inject one; None = ChannelRoots.roots on opts.job_device)
-        self._job_roots = None
-        self.job_roots_fn = None
-        # the template's trees, made by the first new_block when opts.template_device is set; `template_tree_fn`
-        # replaces its device path (tests inject one; None = MerkleTree.tree on opts.template_device)
-        self._template_tree = None
-        self.template_tree_fn = None
-        # the handshake batcher, made by the first Noise connection when opts.handshake_device is set;
-        # `handshake_mul_fn` replaces its device path (tests inject one; None = Secp256k1Mul.mul on that device)
-        self._handshakes = None
-        self.handshake_mul_fn = None
-        # the frame sealer, made by the first _make_job when opts.seal_device is set and Noise is on; `seal_fn`
-        # replaces its configured path (tests inject one; None = FrameSeal.seal on opts.seal_device)
-        self._sealer = None
-        self.seal_fn = None
+        # the CPU-or-GPU paths (_PATH_HOME), each made on first use when its opts.<prefix>_device is set: the
+        # batcher by validate_async, the fan-out and (with Noise) the sealer by _make_job, the trees by new_block, the
+        # handshakes by a Noise connection. The second attribute replaces the path's device call (tests inject one;
+        # None = the path's op on that device).
+        self._batcher = self._job_roots = self._template_tree = self._handshakes = self._sealer = None
+        self.verify_hasher = self.job_roots_fn = self.template_tree_fn = self.handshake_mul_fn = self.seal_fn = None
         self._branches_of: BlockTemplate | None = None  # the block whose merkle branches are cached below
         self._branches: list[bytes] = []
         self._init_metrics(registry)
@@ -302,16 +297,14 @@ class PoolServer:
                 await asyncio.wait_for(s.wait_closed(), 2)
             except asyncio.TimeoutError:
                 pass
-        if self._handshakes is not None:
-            await self._handshakes.stop()  # waiting handshakes get their results (from the CPU)
-        if self._batcher is not None:
-            await self._batcher.close()  # pending submits are answered (on the CPU) before the journal closes
-        if self._job_roots is not None:
-            self._job_roots.close()
-        if self._template_tree is not None:
-            self._template_tree.close()
-        if self._sealer is not None:
-            self._sealer.close()
+        # waiting handshakes get their results, then pending submits their verdicts (both from the CPU), before the
+        # journal closes
+        for prefix in ("handshake", "verify", "job", "template", "seal"):
+            path = getattr(self, _PATH_HOME[prefix][0])
+            if path is not None and PATHS[prefix].batched:
+                await path.close()
+            elif path is not None:
+                path.close()
         self._hash_pool.shutdown(wait=False, cancel_futures=True)
         self.journal.close()
 
@@ -359,11 +352,7 @@ class PoolServer:
     def new_block(self) -> PoolJob:
         self.block = self.templates.next_block()
         if self.opts.template_device:  # both trees in one call, before the first coinbase_parts needs the commitment
-            if self._template_tree is None:
-                from otedama_amd.pool.templatetree import TemplateTree
-
-                self._template_tree = TemplateTree(self, device_tree=self.template_tree_fn)
-            self.block.set_tree(*self._template_tree.compute(self.block.txids, self.block.wtxids))
+            self.block.set_tree(*self._path("template").compute(self.block.txids, self.block.wtxids))
         self.jobs.clear()
         self._seen.clear()
         job = self._make_job(clean=True)
@@ -390,11 +379,7 @@ class PoolServer:
         v2 = list(self._v2)
         roots = self._standard_roots(job, v2) if self.opts.job_device else {}
         if self.opts.seal_device and self.opts.noise and v2:  # the frames of all of them sealed in one call
-            if self._sealer is None:
-                from otedama_amd.pool.frameseal import FrameSealer
-
-                self._sealer = FrameSealer(self, device_seal=self.seal_fn)
-            with self._sealer.corked(v2):
+            with self._path("seal").corked(v2):
                 for c in v2:
                     c.send_job(job, roots.get(c))
             return job
@@ -417,13 +402,9 @@ class PoolServer:
                     if ch not in c.extended]
         if not gathered:
             return {}
-        if self._job_roots is None:
-            from otedama_amd.pool.jobroots import JobRoots
-
-            self._job_roots = JobRoots(self, device_roots=self.job_roots_fn)
         sj = ShareJob(job.coinb1, job.coinb2, EN1_SIZE + EN2_SIZE, job.block.prev_hash, job.block.nbits, job.branches)
         out: dict = {}
-        for (c, ch, _prefix), root in zip(gathered, self._job_roots.roots(sj, [g[2] for g in gathered])):
+        for (c, ch, _prefix), root in zip(gathered, self._path("job").roots(sj, [g[2] for g in gathered])):
             out.setdefault(c, {})[ch] = root
         return out
 
@@ -550,12 +531,24 @@ class PoolServer:
                 out.append(self._finish(worker, job_id, job, hdr, h, item[2]))
         return out
 
-    def _get_batcher(self):
-        if self._batcher is None:
-            from otedama_amd.pool.microbatch import ShareBatcher
+    def _path(self, prefix: str):
+        """The pool's path of that option prefix (pool/devicepath.py PATHS), made on first use with the injected
+        device call, if any. The module is imported here, and its class looked up here, not before."""
+        attr, inject, module, cls = _PATH_HOME[prefix]
+        path = getattr(self, attr)
+        if path is None:
+            path = getattr(importlib.import_module(f"otedama_amd.pool.{module}"), cls)(self, getattr(self, inject))
+            setattr(self, attr, path)
+        return path
 
-            self._batcher = ShareBatcher(self, device_hasher=self.verify_hasher)
-        return self._batcher
+    def _path_stats(self, prefix: str) -> dict:
+        """The path's object of /api/v1/pool: its device, whether the configured path is in use (False when the
+        feature is off, and after a device error has turned a GPU path off), and its counters."""
+        path = getattr(self, _PATH_HOME[prefix][0])
+        return path.stats() if path is not None else PATHS[prefix].off_stats(getattr(self.opts, f"{prefix}_device"))
+
+    def _get_batcher(self):
+        return self._batcher or self._path("verify")
 
     def share_target(self, difficulty: float) -> bytes:
         """Share target for a difficulty, clamped to 2^256-1 (below ~diff1/2^256 the target would overflow)."""
@@ -729,52 +722,19 @@ class PoolServer:
                 "settled": self.vardiff.settled(w.vd, mutate=False)}
 
     def verify_stats(self) -> dict:
-        """The ``verify`` object of /api/v1/pool: the micro-batcher's device, whether the configured path is in use
-        (False when the feature is off, and after a device error has turned a GPU path off), and its counters."""
-        if self._batcher is not None:
-            return self._batcher.stats()
-        return {"device": self.opts.verify_device, "enabled": False, "batches": 0, "gpu_shares": 0, "cpu_shares": 0,
-                "last_batch": 0, "max_batch": 0, "device_errors": 0}
+        return self._path_stats("verify")
 
     def jobs_stats(self) -> dict:
-        """The ``jobs`` object of /api/v1/pool: the job fan-out's device, whether the configured path is in use
-        (False when the feature is off, and after a device error has turned a GPU path off), and its counters."""
-        if self._job_roots is not None:
-            return self._job_roots.stats()
-        return {"device": self.opts.job_device, "enabled": False, "fanouts": 0, "gpu_channels": 0, "cpu_channels": 0,
-                "last_channels": 0, "last_ms": 0.0, "device_errors": 0}
+        return self._path_stats("job")
 
     def template_stats(self) -> dict:
-        """The ``template`` object of /api/v1/pool: the template tree's device, whether the configured path is in
-        use (False when the feature is off, and after a device error has turned a GPU path off), and its counters."""
-        if self._template_tree is not None:
-            return self._template_tree.stats()
-        return {"device": self.opts.template_device, "enabled": False, "trees": 0, "gpu_leaves": 0, "cpu_leaves": 0,
-                "last_leaves": 0, "last_ms": 0.0, "device_errors": 0}
+        return self._path_stats("template")
 
     def handshake_stats(self) -> dict:
-        """The ``handshake`` object of /api/v1/pool: the handshake batcher's device, whether the configured path is
-        in use (False when the feature is off, and after a device error has turned a GPU path off), and its
-        counters."""
-        if self._handshakes is not None:
-            return self._handshakes.stats()
-        return {"device": self.opts.handshake_device, "enabled": False, "batches": 0, "gpu_handshakes": 0,
-                "cpu_handshakes": 0, "last_batch": 0, "max_batch": 0, "last_ms": 0.0, "device_errors": 0}
+        return self._path_stats("handshake")
 
     def seal_stats(self) -> dict:
-        """The ``seal`` object of /api/v1/pool: the frame sealer's device, whether the configured path is in use
-        (False when the feature is off, and after a device error has turned a GPU path off), and its counters."""
-        if self._sealer is not None:
-            return self._sealer.stats()
-        return {"device": self.opts.seal_device, "enabled": False, "batches": 0, "gpu_frames": 0, "cpu_frames": 0,
-                "last_frames": 0, "last_ms": 0.0, "device_errors": 0}
-
-    def _get_handshakes(self):
-        if self._handshakes is None:
-            from otedama_amd.pool.handshakes import HandshakeBatcher
-
-            self._handshakes = HandshakeBatcher(self, device_mul=self.handshake_mul_fn)
-        return self._handshakes
+        return self._path_stats("seal")
 
     def stats(self) -> dict:
         now = time.monotonic()
@@ -789,11 +749,7 @@ class PoolServer:
             "validate_ms": {"p50": self.validation_ms(0.5), "p95": self.validation_ms(0.95),
                             "p99": self.validation_ms(0.99), "samples": len(self._validate_ms)},
             "fixed_difficulty": self.opts.fixed_difficulty,
-            "verify": self.verify_stats(),
-            "jobs": self.jobs_stats(),
-            "template": self.template_stats(),
-            "handshake": self.handshake_stats(),
-            "seal": self.seal_stats(),
+            **{spec.api_key: self._path_stats(prefix) for prefix, spec in PATHS.items()},
             "new_block_at": list(self.new_block_at)[-64:],
             # per live connection: the difficulty in force, how often vardiff moved it, and when it last moved
             # (seconds after the channel opened: the time vardiff took to reach the difficulty it holds)
@@ -827,7 +783,7 @@ class PoolServer:
                 reader, writer = await noise.server_handshake(
                     reader, writer, self._noise_static, self._noise_cert, suite=self.opts.noise_suite or None,
                     static_x=self._noise_static_x,
-                    ec_batcher=self._get_handshakes() if self.opts.handshake_device else None)
+                    ec_batcher=self._path("handshake") if self.opts.handshake_device else None)
             except (noise.NoiseError, asyncio.IncompleteReadError, asyncio.TimeoutError, ConnectionError, OSError):
                 writer.close()
                 self.reject_reasons["noise-handshake"] = self.reject_reasons.get("noise-handshake", 0) + 1
