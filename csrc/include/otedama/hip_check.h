@@ -1,6 +1,7 @@
-// HIP error and pointer-alignment checks shared by the HIP translation units (host side only).
+// HIP error and pointer-alignment checks shared by the HIP translation units and the bindings (host side only; the
+// runtime's API header is plain C++).
 #pragma once
-#include <hip/hip_runtime.h>
+#include <hip/hip_runtime_api.h>
 
 #include <cstdint>
 #include <stdexcept>

@@ -1,8 +1,11 @@
-// Launch entry points of the gfx950 search kernels (csrc/kernels/*.hip) and the device queries, declared once for
-// the files that define them, the GPU miner and the Python bindings. The X11 stage launchers are in
-// otedama/x11_launch.h. The first part is plain C++ (bindings.cpp is compiled by the host compiler); the launches
-// that take a hipStream_t are visible to HIP translation units only.
+// Launch entry points of the gfx950 kernels (csrc/kernels/*.hip) and the device queries, declared once for the files
+// that define them, the GPU miner and the Python bindings. The X11 stage launchers are in otedama/x11_launch.h.
+// Plain C++: the runtime's API header and its vector types need no HIP compiler, so bindings.cpp, which the host
+// compiler builds, calls the launches itself. Every launch enqueues on `stream` and synchronises nothing.
 #pragma once
+#include <hip/hip_runtime_api.h>
+#include <hip/hip_vector_types.h>
+
 #include <cstdint>
 #include <string>
 
@@ -31,72 +34,6 @@ int gpu_device_count();
 std::string gpu_arch_name(int device);
 int gpu_cu_count(int device);
 
-// Launches for the Python ops layer (all in runtime/ops_launch.hip; torch-owned buffers and streams): pointers and
-// the stream arrive as integers, a HIP error is thrown as std::runtime_error. Searches: hits go to the legacy
-// device-memory slots after out[0]; no abort word.
-void py_launch_sha256d(const Sha256dParams& p, uint32_t base, uint64_t count, uintptr_t out, uint32_t cap, int grid,
-                       uintptr_t stream);
-void py_launch_sha256d_k(const Sha256dParamsK& p, uint32_t base, uint64_t count, uintptr_t out, uint32_t cap, int grid,
-                         uintptr_t stream);
-void py_launch_sha256d_v(const Sha256dParamsV& p, uintptr_t vars, uint32_t base, uint64_t count, uintptr_t out,
-                         uint32_t cap, int grid, uintptr_t stream, int block, int chains);
-void py_launch_scrypt(const ScryptParams& p, uint32_t base, uint32_t count, uintptr_t xbuf, uintptr_t scratch, int gap,
-                      uintptr_t out, uint32_t cap, int grid, uintptr_t stream);
-void py_launch_x11_stage(const X11Params& p, int stage, uint32_t base, uintptr_t H, uint32_t stride, uint32_t n,
-                         uintptr_t out, uint32_t cap, uintptr_t stream);
-void py_launch_x11(const X11Params& p, uint32_t base, uintptr_t H, uint32_t stride, uint32_t n, uintptr_t out,
-                   uint32_t cap, uintptr_t stream);
-
-// Digest ops (kernels in digest_batch.hip): n unrelated 80-byte headers at headers + 80 * i -> n digests at out + 32 * i, in
-// the byte order PowAlgorithm.hash returns. Same conventions as above; both arrays must be 16-byte aligned.
-void py_launch_sha256d_digest(uintptr_t headers, uint32_t n, uintptr_t out, uintptr_t stream);
-void py_launch_scrypt_digest(uintptr_t headers, uint32_t n, uintptr_t xbuf, uintptr_t scratch, int gap, uintptr_t out,
-                             int grid, uintptr_t stream);
-void py_launch_x11_digest(uintptr_t headers, uintptr_t H, uint32_t stride, uint32_t n, uintptr_t out,
-                          uintptr_t stream);
-
-// Share verification (kernels in share_verify.hip; layouts in otedama/share_job.h): n 32-byte share records against one
-// uploaded job block -> n 80-byte headers, and n digests against a table of n_targets 32-byte targets -> n verdict
-// bytes. Same conventions as above; every array but the verdicts must be 16-byte aligned.
-void py_launch_share_headers(uintptr_t job, uintptr_t records, uint32_t n, uintptr_t headers, uintptr_t stream);
-void py_launch_share_verdict(uintptr_t job, uintptr_t records, uintptr_t digests, uintptr_t targets,
-                             uint32_t n_targets, uint32_t n, uintptr_t verdicts, uintptr_t stream);
-
-// Live share verification (otd_share_pack of share_verify.hip): the headers and digests of the chain above -> n
-// 128-byte ShareResult records, with the compares done there. Every array is 16-byte aligned.
-void py_launch_share_pack(uintptr_t job, uintptr_t records, uintptr_t headers, uintptr_t digests, uintptr_t targets,
-                          uint32_t n_targets, uint32_t n, uintptr_t results, uintptr_t stream);
-
-// Channel roots (otd_channel_roots of channel_roots.hip): n 16-byte extranonce prefixes (the job's first en_size bytes
-// of each are used) against one uploaded job block -> n 32-byte merkle roots at roots + 32 * i, in header byte order.
-// Same conventions as above; every array is 16-byte aligned.
-void py_launch_channel_roots(uintptr_t job, uintptr_t prefixes, uint32_t n, uintptr_t roots, uintptr_t stream);
-
-// Template tree (otd_merkle_tree of merkle_tree.hip; rows, limits and the CPU twin: otedama/merkle_tree.h): t trees of
-// n 32-byte leaves at leaves + 32 * n * y -> 1 + depth rows of 32 bytes per tree at out + 32 * (1 + depth) * y.
-// scratch: 32 bytes per 512-leaf chunk per tree (t * ceil(n / 512) rows), read only when n > 512; may be 0 otherwise.
-// Same conventions as above; every array is 16-byte aligned.
-void py_launch_merkle_tree(uintptr_t leaves, uint32_t t, uint32_t n, uintptr_t scratch, uintptr_t out,
-                           uintptr_t stream);
-
-// secp256k1 multiplication (otd_secp256k1_mul of secp256k1_mul.hip; rows, limits and the CPU twin:
-// otedama/secp256k1.h): n 128-byte rows -> n 48-byte rows. Same conventions as above; both arrays are 16-byte aligned.
-void py_launch_secp256k1_mul(uintptr_t rows, uint32_t n, uintptr_t out, uintptr_t stream);
-
-// Frame sealing (otd_aead_seal of aead_seal.hip; heads, regions, limits and the CPU twin: otedama/aead.h): n heads and
-// their data in one input buffer -> each frame's tag and ciphertext in its region of the output. Same conventions as
-// above; both buffers are 16-byte aligned. otd_poly1305_rows is the test entry: n 160-byte rows -> n 16-byte tags.
-void py_launch_aead_seal(uintptr_t in, uint64_t in_bytes, uint32_t n, uintptr_t out, uint64_t out_bytes,
-                         uintptr_t stream);
-void py_launch_poly1305_rows(uintptr_t rows, uint32_t n, uintptr_t tags, uintptr_t stream);
-
-}  // namespace otedama
-
-#ifdef __HIPCC__
-#include <hip/hip_runtime.h>
-
-namespace otedama {
-
 // `count` nonces from `base` on `grid` blocks of 256 (sha256d_search.hip, sha256d_search_v.hip); hits go to `sink`.
 hipError_t launch_sha256d_search(const Sha256dParams& p, uint32_t base, uint64_t count, const HitSink& sink, int grid,
                                  hipStream_t stream);
@@ -113,8 +50,10 @@ hipError_t launch_scrypt_search(const ScryptParams& p, uint32_t base, uint32_t c
 hipError_t launch_scrypt_romix(uint32_t count, uint4* xbuf, uint4* scratch, int gap, const HitSink& sink, int grid,
                                hipStream_t stream);
 
-// Digests of n unrelated headers (layout above). Each returns hipErrorInvalidValue, before launching anything, for
-// n == 0, n above the stated capacity, a null pointer or a header / digest array that is not 16-byte aligned.
+// Digest ops (kernels in digest_batch.hip): n unrelated 80-byte headers at headers + 80 * i -> n digests at
+// out + 32 * i, in the byte order PowAlgorithm.hash returns. Each returns hipErrorInvalidValue, before launching
+// anything, for n == 0, n above the stated capacity, a null pointer or a header / digest array that is not 16-byte
+// aligned.
 hipError_t launch_sha256d_digest(const uint8_t* headers, uint32_t n, uint8_t* out, hipStream_t s);
 // xbuf: grid * 256 * 128 bytes. scratch: scrypt_scratch_bytes(grid, gap). One header per lane slot.
 hipError_t launch_scrypt_digest(const uint8_t* headers, uint32_t n, void* xbuf, void* scratch, int gap,
@@ -123,32 +62,44 @@ hipError_t launch_scrypt_digest(const uint8_t* headers, uint32_t n, void* xbuf, 
 hipError_t launch_x11_digest(const uint8_t* headers, uint64_t* H, uint32_t stride, uint32_t n, uint8_t* out,
                              hipStream_t s);                              // n <= stride
 
-// Share verification. Each returns hipErrorInvalidValue, before launching anything, for n == 0, an empty target
-// table, a null pointer or an array (the job block included, the verdicts excepted) that is not 16-byte aligned.
-// job: a device copy of a ShareJobBlock.
+// Share verification (kernels in share_verify.hip; layouts in otedama/share_job.h): n 32-byte share records against
+// one uploaded job block (job: a device copy of a ShareJobBlock) -> n 80-byte headers, and n digests against a table
+// of n_targets 32-byte targets -> n verdict bytes. Each returns hipErrorInvalidValue, before launching anything, for
+// n == 0, an empty target table, a null pointer or an array (the job block included, the verdicts excepted) that is
+// not 16-byte aligned.
 hipError_t launch_share_headers(const void* job, const uint8_t* records, uint32_t n, uint8_t* headers, hipStream_t s);
 hipError_t launch_share_verdict(const void* job, const uint8_t* records, const uint8_t* digests,
                                 const uint8_t* targets, uint32_t n_targets, uint32_t n, uint8_t* verdicts,
                                 hipStream_t s);
-// The same conventions; here every array, the results included, is 16-byte aligned.
+// Live share verification (otd_share_pack): the headers and digests of the chain above -> n 128-byte ShareResult
+// records, with the compares done there. The same conventions; here every array, the results included, is 16-byte
+// aligned.
 hipError_t launch_share_pack(const void* job, const uint8_t* records, const uint8_t* headers, const uint8_t* digests,
                              const uint8_t* targets, uint32_t n_targets, uint32_t n, uint8_t* results, hipStream_t s);
-// Channel roots: hipErrorInvalidValue, before launching anything, for n == 0, a null pointer or an array (the job
-// block included) that is not 16-byte aligned.
+// Channel roots (otd_channel_roots of channel_roots.hip): n 16-byte extranonce prefixes (the job's first en_size bytes
+// of each are used) against one uploaded job block -> n 32-byte merkle roots at roots + 32 * i, in header byte order.
+// hipErrorInvalidValue, before launching anything, for n == 0, a null pointer or an array (the job block included)
+// that is not 16-byte aligned.
 hipError_t launch_channel_roots(const void* job, const uint8_t* prefixes, uint32_t n, uint8_t* roots, hipStream_t s);
-// Template tree: hipErrorInvalidValue, before launching anything, for t == 0 or above kMerkleTreeMaxTrees, n == 0 or
+// Template tree (otd_merkle_tree of merkle_tree.hip; rows, limits and the CPU twin: otedama/merkle_tree.h): t trees of
+// n 32-byte leaves at leaves + 32 * n * y -> 1 + depth rows of 32 bytes per tree at out + 32 * (1 + depth) * y.
+// scratch: 32 bytes per 512-leaf chunk per tree (t * ceil(n / 512) rows), read only when n > 512; may be null
+// otherwise. hipErrorInvalidValue, before launching anything, for t == 0 or above kMerkleTreeMaxTrees, n == 0 or
 // above kMerkleTreeMaxLeaves, a null or not 16-byte aligned leaves or out, and the same of scratch when n > 512.
 hipError_t launch_merkle_tree(const uint8_t* leaves, uint32_t t, uint32_t n, uint8_t* scratch, uint8_t* out,
                               hipStream_t s);
-// secp256k1 multiplication: hipErrorInvalidValue, before launching anything, for n == 0 or above kSecpMaxRows, and a
-// null or not 16-byte aligned rows or out.
+// secp256k1 multiplication (otd_secp256k1_mul of secp256k1_mul.hip; rows, limits and the CPU twin:
+// otedama/secp256k1.h): n 128-byte rows -> n 48-byte rows. hipErrorInvalidValue, before launching anything, for
+// n == 0 or above kSecpMaxRows, and a null or not 16-byte aligned rows or out.
 hipError_t launch_secp256k1_mul(const uint8_t* rows, uint32_t n, uint8_t* out, hipStream_t s);
-// Frame sealing: hipErrorInvalidValue, before launching anything, for n == 0 or above kSealMaxFrames, a null or not
-// 16-byte aligned buffer, an input shorter than its n heads, and a buffer size that is no multiple of 16 or is 4 GiB
-// or more. The heads themselves are on the device: the kernel skips a lane whose head breaks the rules.
+// Frame sealing (otd_aead_seal of aead_seal.hip; heads, regions, limits and the CPU twin: otedama/aead.h): n heads and
+// their data in one input buffer -> each frame's tag and ciphertext in its region of the output.
+// hipErrorInvalidValue, before launching anything, for n == 0 or above kSealMaxFrames, a null or not 16-byte aligned
+// buffer, an input shorter than its n heads, and a buffer size that is no multiple of 16 or is 4 GiB or more. The
+// heads themselves are on the device: the kernel skips a lane whose head breaks the rules. otd_poly1305_rows is the
+// test entry: n 160-byte rows -> n 16-byte tags.
 hipError_t launch_aead_seal(const uint8_t* in, uint64_t in_bytes, uint32_t n, uint8_t* out, uint64_t out_bytes,
                             hipStream_t s);
 hipError_t launch_poly1305_rows(const uint8_t* rows, uint32_t n, uint8_t* tags, hipStream_t s);
 
 }  // namespace otedama
-#endif

@@ -1,6 +1,6 @@
-// gfx950 X11 stage launchers (csrc/kernels/x11_stages_{a,b}.hip); HIP translation units only.
+// gfx950 X11 stage launchers (csrc/kernels/x11_stages_{a,b}.hip), for the kernel files, the miner and the bindings.
 #pragma once
-#include <hip/hip_runtime.h>
+#include <hip/hip_runtime_api.h>
 
 #include <cstdint>
 

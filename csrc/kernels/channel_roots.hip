@@ -6,18 +6,19 @@
 //                      coinbase SHA-256d from the job's midstate (the tail blocks with the lane's prefix patched in),
 //                      the merkle fold over the job's branches, two 16-byte stores at roots + 32 * i.
 //
-// The coinbase-and-fold body is otd_share_headers' (share_verify.hip), copied and not shared: that file's kernels
-// keep their gfx950 code byte for byte, so nothing that was measured for them has to be measured again
-// (docs/KERNELS.md, "Channel roots"). The same rules hold here. Everything that comes from the job block is the
-// same for every lane: the template words, the branches, the midstate and the counts are read through indices formed
-// from kernel arguments and loop counters only, so they are scalar loads into SGPRs. The loops over tail blocks and
-// branches stay rolled (their trip counts are job values); the 64 rounds inside them unroll, so no array is indexed
-// with a run-time value and nothing goes to scratch.
+// The coinbase-and-fold body is otd_share_headers' (share_verify.hip), copied and not shared: sharing it was
+// measured and cost the latency-bound case 2 us (docs/KERNELS.md, "Channel roots"). The SHA-256 helpers under it are
+// shared (sha256_fold_dev.h), with the gfx950 code unchanged. The same rules hold here. Everything that comes from
+// the job block is the same for every lane: the template words, the branches, the midstate and the counts are read
+// through indices formed from kernel arguments and loop counters only, so they are scalar loads into SGPRs. The loops
+// over tail blocks and branches stay rolled (their trip counts are job values); the 64 rounds inside them unroll, so
+// no array is indexed with a run-time value and nothing goes to scratch.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "cdna_bitops.h"
+#include "sha256_fold_dev.h"
 #include "otedama/hip_check.h"
 #include "otedama/search_launch.h"
 #include "otedama/share_job.h"
@@ -25,47 +26,6 @@
 namespace {
 using namespace otedama_dev;
 using otedama::ShareJobBlock;
-
-// The second block of every 64-byte message (cur | branch) is the padding block {0x80000000, 0 x 14, 512}: its
-// schedule and K + W are compile-time constants, so only the round function remains.
-struct PadKW {
-  uint32_t kw[64];
-};
-__device__ constexpr uint32_t c_ror(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
-__device__ constexpr PadKW pad64_kw() {
-  uint32_t w[64] = {};
-  w[0] = 0x80000000u;
-  w[15] = 512u;
-  for (int t = 16; t < 64; ++t) {
-    const uint32_t a = w[t - 15], b = w[t - 2];
-    w[t] = (c_ror(b, 17) ^ c_ror(b, 19) ^ (b >> 10)) + w[t - 7] + (c_ror(a, 7) ^ c_ror(a, 18) ^ (a >> 3)) + w[t - 16];
-  }
-  PadKW r = {};
-  for (int t = 0; t < 64; ++t) r.kw[t] = sha256_k(t) + w[t];
-  return r;
-}
-
-__device__ __forceinline__ void sha256_compress_pad64(uint32_t st[8]) {
-  constexpr PadKW kPad64 = pad64_kw();
-  uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
-#pragma unroll
-  for (int t = 0; t < 64; ++t) {
-    const uint32_t t1 = h + bS1(e) + ch(e, f, g) + kPad64.kw[t];
-    const uint32_t t2 = bS0(a) + maj(a, b, c);
-    h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
-  }
-  st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h;
-}
-
-// SHA-256 of the 32-byte digest whose big-endian words are in[8]: one padded block.
-__device__ __forceinline__ void sha256_of_digest(const uint32_t in[8], uint32_t out[8]) {
-  const uint32_t blk[16] = {in[0], in[1], in[2], in[3], in[4], in[5], in[6], in[7], 0x80000000u, 0, 0, 0, 0, 0, 0, 256u};
-#pragma unroll
-  for (int k = 0; k < 8; ++k) out[k] = kSha256IVd[k];
-  sha256_compress(out, blk);
-}
-
-__device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
 }  // namespace
 

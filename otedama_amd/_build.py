@@ -36,7 +36,6 @@ HIP_SOURCES = [
     "kernels/secp256k1_mul.hip",
     "kernels/aead_seal.hip",
     "runtime/gpu_miner.hip",
-    "runtime/ops_launch.hip",
 ]
 CXX_SOURCES = [
     "cpu/sha256_cpu.cpp",
@@ -121,8 +120,10 @@ def build(verbose: bool = False, jobs: int | None = None, force: bool = False) -
         obj = BUILD / (rel.replace("/", "_") + ".o")
         objs.append(obj)
         if force or _stale(obj, src, deps):
-            tasks.append(["g++", *common, "-march=x86-64-v2", "-I/opt/rocm/include", f"-I{py_inc}", f"-I{pybind11.get_include()}",
-                          "-fvisibility=hidden", "-c", str(src), "-o", str(obj)])
+            # __HIP_PLATFORM_AMD__: the bindings include the HIP runtime's API header (plain C++) for the launches
+            tasks.append(["g++", *common, "-march=x86-64-v2", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                          f"-I{py_inc}", f"-I{pybind11.get_include()}", "-fvisibility=hidden", "-c", str(src), "-o",
+                          str(obj)])
     n = jobs or min(8, os.cpu_count() or 4)
     with cf.ThreadPoolExecutor(max_workers=n) as ex:
         for f in [ex.submit(_compile, t, verbose) for t in tasks]:
